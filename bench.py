@@ -18,7 +18,10 @@ over one batch of synthetic frames already resident in HBM.
 the GPU); under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` it is
 one of the ranks.  --gpus must equal the world size.  Prints ONE JSON line on rank 0.
 
-Beside the contract line's own fields the N = 1 line carries (after the timed region, which they do not touch):
+A plain N = 1 run sets up, warms up, times --steps steps and prints the contract line (metric, value, unit, higher_is_better,
+dtype, ms_per_step, the configuration); --dump-outputs DIR writes the symbols of the last timed step as DIR/symbols.npy.
+With --full the N = 1 line also carries (after the timed region, which they do not touch) the HIP-event kernel time and the
+roofline (live clock, PMC traffic, achievable HBM, power), the bit error rate, cpu_baseline with the oracle gate, and:
   configs        BASELINE configs[2] (base-band I/Q, n = 1024, on the fs = 100 kHz pass-band stream; the firmware-window
                  mode beside it) and configs[3] (UC_STREAM, D = 8, replayed from a captured hipGraph; the eager rate
                  beside it), each with ms_per_step, kernel time by HIP events and both rooflines
@@ -81,7 +84,17 @@ def parse_args(argv=None):
     ap.add_argument("--single-process", action="store_true",
                     help="--gpus N in ONE process: a uc_group over N devices (include/uchirp.h), as a C host would drive the node "
                          "(tests/c/host_multi.c); the default is one process per GPU")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: also run everything beside the headline behind the timed region -- roofline (HIP-event kernel "
+                         "time, live clock, PMC traffic, achievable HBM), power, configs[2] / configs[3], hello_world1, receive, "
+                         "cpu_baseline -- and their gates; a plain run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (the arrays its caller receives) as "
+                         "DIR/<name>.npy in float32; above %d MB in all, a fixed seeded sample of their rows" % (DUMP_BYTES // 10**6))
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 class Watchdog:
@@ -264,6 +277,8 @@ def single_process(args):
     km = np.array([[a.elapsed_time(b) for a, b in row] for row in evs]).mean(axis=0)       # kernel ms by device
     last = gat[(args.steps - 1) % NBUF]
     host = [g.cpu().numpy() for g in last]
+    if args.dump_outputs:                     # the gathered symbol stream (every device holds it: digests below)
+        dump_outputs(args.dump_outputs, {"symbols": host[0]})
     digs = [hashlib.sha256(h.tobytes()).hexdigest() for h in host]
     gate_failures = []
     if len(set(digs)) != 1:
@@ -519,8 +534,11 @@ def main():
         dist.barrier()
     sync()
 
+    # A plain N = 1 run does what its headline needs and no more; the rest of the line -- kernel time, roofline, power, the
+    # side legs and their gates -- is --full's.  The N > 1 line keeps its per-rank figures and decode gates (its workload's).
+    extra = args.full or multi
     # per-launch kernel time: HIP events on the stream the kernel is launched on
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) if have_gpu else (None, None)
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) if have_gpu and extra else (None, None)
           for _ in range(args.steps)]
     t0 = time.perf_counter()
     for k in range(args.steps):
@@ -534,12 +552,15 @@ def main():
         dist.barrier()
     sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:       # what the caller of the last timed step holds: the (gathered) symbol stream
+        last = (args.steps - 1) % NBUF
+        dump_outputs(args.dump_outputs, {"symbols": gathered2[last] if multi else sym2[last]})
     wd.mark("checks behind the timed region", args.steps - 1)
     # Sustained run behind the timed region (untimed, N = 1 only): the SMU's power figure is a moving average over about a
     # second, so the 40 ms of the timed region cannot show it; 1.5 s of back-to-back launches can.  Reports the socket power
     # and the SMU's clock over the last 0.5 s, and the rate the kernel holds meanwhile.
     power_rec = None
-    if eng is not None and not multi and rank == 0 and args.sustain_s > 0:
+    if eng is not None and not multi and rank == 0 and args.full and args.sustain_s > 0:
         power = PowerSampler(torch, device)
         power.start()
         t_s = time.perf_counter()
@@ -583,10 +604,10 @@ def main():
             dist.all_gather(dd, dig.to(device))
             digs = [d.cpu() for d in dd]
         assert all(torch.equal(d, digs[0]) for d in digs), "ranks hold different gathered symbol streams"
-    kern_ms = float(np.mean([a.elapsed_time(b) for a, b in ev])) if have_gpu else None
+    kern_ms = float(np.mean([a.elapsed_time(b) for a, b in ev])) if have_gpu and extra else None
     # the clock the chip held under the kernel of the timed region, measured now, on this box (every rank: its own)
     clk_live = None
-    if eng is not None:
+    if eng is not None and extra:
         clk_live = live_clock(eng, lambda: eng.process(frames, want_stats=False, symbols_out=sym2[0], stream=stream.cuda_stream))
     local_ms = elapsed_local / args.steps * 1e3
     per_rank = None
@@ -642,7 +663,7 @@ def main():
                                          "symbol decision (rx_real), SNR %.0f dB" % (nf, args.snr),
                              "frames_per_gpu": nf, "frame_len": N, "variant": "rx_real",
                              "parallelism": "frame-sharded x%d, RCCL all-gather of symbols" % world}
-        if have_gpu:
+        if have_gpu and extra:
             achieved = nf * BYTES_PER_FRAME / (kern_ms * 1e-3) / 1e9
             # HBM bytes per launch from the committed PMC passes (FETCH_SIZE x2 on gfx950 + WRITE_SIZE,
             # collected with rocprofv3 --pmc in their own runs: profiles/*_hbm_traffic.json), scaled to
@@ -717,14 +738,14 @@ def main():
             out["rccl_world"] = int(grp.world) if grp is not None else None
             out["scaling_note"] = ("no 1 -> 8 curve has been measured by the builder (one-GPU boxes only): the first real "
                                    "N > 1 numbers are the driver's")
-        else:
+        elif args.full:
             # correctness figure of the measured run: decoded symbols vs transmitted bits.  ~23 % is EXPECTED here:
             # configs[1] runs the firmware's literal TIME_FRAME = 0.0205 s reference tables against frames that
             # sweep over the whole 26.2 ms frame; GPU == oracle is the gate (below), the matched sweep is configs[4]
             out["bit_error_rate_vs_transmitted"] = float((symbols != sent).float().mean().item())
             out["bit_error_rate_note"] = ("expected ~0.23: literal TIME_FRAME reference (SURVEY Q4) vs full-frame sweeps; "
                                           "the oracle has the same errors (symbols_equal_oracle_head4096_clear)")
-        if not multi and have_gpu and not args.no_configs:
+        if not multi and have_gpu and args.full and not args.no_configs:
             cfgs = {}
             for name, fn in (("configs[2]", lambda: config2_iq(args, device, stream, torch, mag_mean)),
                              ("configs[3]", lambda: config3_stream(args, frames, device, torch))):
@@ -743,7 +764,7 @@ def main():
                 gate_failures.append("configs[3]: graph replay differs from the eager launch")
             if c3.get("head_rel_err_vs_oracle", 0.0) > 2e-5 or c3.get("head_peak_offsets_equal_oracle") is False:
                 gate_failures.append("configs[3]: stream head differs from the oracle")
-        if not multi and have_gpu and not args.no_hello1:
+        if not multi and have_gpu and args.full and not args.no_hello1:
             t_c = time.perf_counter()
             try:
                 h1 = hello_world1(args, device, torch, mag_mean)
@@ -762,7 +783,7 @@ def main():
                 out["scale_anchor"] = {"workload": "configs[4] at world size 1 (the workload of the --gpus N > 1 lines)",
                                        "n_gpus": 1, "value": h1["value"], "unit": "frames/s", "ms_per_step": h1["ms_per_step"],
                                        "how": "UC_BENCH_HELLO=1 python bench.py prints this leg as its contract line"}
-        if not multi and have_gpu and not args.no_receive:
+        if not multi and have_gpu and args.full and not args.no_receive:
             t_c = time.perf_counter()
             try:
                 rx = receive_leg(args, device, torch)
@@ -778,7 +799,7 @@ def main():
                 gate_failures.append("receive failed: %s" % type(ex).__name__)
             rx["wall_s"] = time.perf_counter() - t_c
             out["receive"] = rx
-        if not multi and have_gpu and not args.no_cpu_baseline:
+        if not multi and have_gpu and args.full and not args.no_cpu_baseline:
             cb = cpu_baseline(frames[: 1 << 19].cpu().numpy(), mag_mean)
             # the oracle as the checker: GPU symbols of the measured run vs float64 oracle
             head, clear = cb.pop("symbols_f64_oracle_head"), cb.pop("clear_head")

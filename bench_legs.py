@@ -420,6 +420,8 @@ def stream_measurement(args, eng, frames, rank, torch):
 
     clock_ramp(launch, torch, args.ramp_ms)
     wall, kern = timed_launches(launch, stream, torch, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"compressed": comp, "peaks": pk})
     ncu, clk = num_cus(torch, x.device), live_clock(eng, launch)
     byts = (x.numel() * 4 + n_out * 4 + n_blocks * 8) / x.numel()
     if rank == 0:
@@ -460,6 +462,8 @@ def side_measurement(args, eng, frames, world, rank, torch):
 
     clock_ramp(launch, torch, args.ramp_ms)
     wall, kern = timed_launches(launch, stream, torch, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"symbols": sym} if want_sym else {"stats": stats})
     ncu, clk = num_cus(torch, frames.device), live_clock(eng, launch)
     if rank == 0:
         print(json.dumps({"metric": "chirp frames/s (%s, side measurement)" % args.variant, "value": nfr / (wall * 1e-3),

@@ -24,6 +24,26 @@ MSG = "Hello World!"
 # rewrites the buffer that gather reads) had to wait for it with the chip idle (20 us per step at world size 1, measured);
 # with three it is the kernel of step k + 3 that depends on gather k, a whole kernel time later.
 NBUF = 3
+DUMP_BYTES = 64 * 10**6             # --dump-outputs: at most this much in all
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array (numpy or a device tensor) as `dirname/<name>.npy`, float32 (float64 stays float64).  Above
+    DUMP_BYTES in all, each array keeps the same share of its rows, drawn with a fixed seed: the same rows in every run of the
+    same arguments."""
+    os.makedirs(dirname, exist_ok=True)
+    width = {k: 8 if str(a.dtype).endswith("float64") else 4 for k, a in arrays.items()}
+    total = sum(int(np.prod(a.shape)) * width[k] for k, a in arrays.items())
+    for name, a in arrays.items():
+        if total > DUMP_BYTES - 4096 * len(arrays):                  # (room for the .npy headers)
+            keep = max(1, a.shape[0] * (DUMP_BYTES - 4096 * len(arrays)) // total)
+            rows = np.unique(np.random.default_rng(0).integers(0, a.shape[0], keep))   # (sorted; O(keep) memory)
+            if not isinstance(a, np.ndarray):                            # a tensor: pick the rows where it lives
+                import torch
+                rows = torch.from_numpy(rows).to(a.device)
+            a = a[rows]
+        a = a if isinstance(a, np.ndarray) else a.cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a.astype(np.float64 if width[name] == 8 else np.float32))
 
 
 def make_device_frames(n_frames, device, seed, snr_db=-10.0, amp=1000.0):

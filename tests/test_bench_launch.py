@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -83,6 +84,37 @@ def test_hello_leg_runs_at_world_size_one():
     assert d["n_gpus"] == 1 and d["config"]["workload"].startswith("configs[4]") and d["decoded_text_first"] == "Hello World!"
 
 
+def test_dump_outputs_writes_the_last_steps_symbols(tmp_path):
+    """--dump-outputs DIR: the symbol stream the last timed step handed its caller, as DIR/symbols.npy in float32 (here the
+    world-size-1 rehearsal without a GPU, whose "decoded" stream is the transmitted one)."""
+    from uchirp import synth
+    p = _run(["--frames", "1170", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+             {"UC_BENCH_REHEARSE": "1", "UC_BENCH_HELLO": "1", "HIP_VISIBLE_DEVICES": "", "ROCR_VISIBLE_DEVICES": ""})
+    assert p.returncode == 0, p.stderr[-2000:]
+    got = np.load(tmp_path / "symbols.npy")
+    sent = synth.hello_kind_stream(0, 1170, "Hello World!")
+    assert got.dtype == np.float32 and np.array_equal(got, np.where(sent == 2, 255, sent).astype(np.float32))
+
+
+def test_steps_must_be_at_least_one():
+    p = _run(["--steps", "0"], {"HIP_VISIBLE_DEVICES": "", "ROCR_VISIBLE_DEVICES": ""})
+    assert p.returncode != 0 and "--steps must be at least 1" in p.stderr
+
+
+def test_dump_outputs_samples_large_outputs_the_same_way_every_time(tmp_path):
+    """Above 64 MB in all, --dump-outputs keeps a fixed, seeded share of every array's rows; float64 stays float64."""
+    import bench_telemetry
+    big = np.arange(12_000_000, dtype=np.int32).reshape(6_000_000, 2)        # 96 MB as float32
+    small = np.linspace(0.0, 1.0, 4_000_000)                                 # 32 MB as float64
+    for d in ("a", "b"):
+        bench_telemetry.dump_outputs(str(tmp_path / d), {"big": big, "small": small})
+    a, b = [np.load(tmp_path / d / "big.npy") for d in ("a", "b")]
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert a.dtype == np.float32 and s.dtype == np.float64 and np.array_equal(a, b)
+    assert a.nbytes + s.nbytes <= bench_telemetry.DUMP_BYTES and a.shape[1] == 2 and len(a) > 1_000_000
+    assert np.array_equal(a[:, 1] - a[:, 0], np.ones(len(a))) and np.all(np.diff(a[:, 0]) > 0)   # whole rows, in order
+
+
 # ---- on the GPU box: the legs of bench.py the driver's 8-GPU run depends on, as fresh child processes -----------------
 
 def _one_line(p):
@@ -129,9 +161,9 @@ def test_gpu_single_process_group_line():
 
 @pytest.mark.gpu
 def test_gpu_default_line_carries_every_single_gpu_config():
-    """The N = 1 contract line (small batch): configs[1] headline + configs[2] (base-band I/Q and firmware windows) +
+    """The N = 1 line with --full (small batch): configs[1] headline + configs[2] (base-band I/Q and firmware windows) +
     configs[3] (eager and graph replay) + hello_world1 + cpu_baseline, all gates green."""
-    d = _one_line(_run(["--frames", "65536", "--steps", "3", "--warmup", "1", "--ramp-ms", "20"], {}))
+    d = _one_line(_run(["--full", "--frames", "65536", "--steps", "3", "--warmup", "1", "--ramp-ms", "20"], {}))
     assert d["n_gpus"] == 1 and d["config"]["workload"].startswith("configs[1]") and d["gates_failed"] == []
     # HBM traffic from the PMC counters, collected in this run (two rocprofv3 child passes): no wasted re-reads
     assert d["roofline"]["bound"] == "hbm" and d["roofline"]["limiter"] in ("hbm", "valu") and d["roofline"]["traffic_source"].startswith("measured in this run")
@@ -152,6 +184,26 @@ def test_gpu_default_line_carries_every_single_gpu_config():
     assert c2["baseband"]["roofline"]["valu"]["clock_source"].startswith("uc_clock_read")
     assert c3["eager"]["roofline"]["valu"]["clock_source"].startswith("uc_clock_read")
     assert d["symbols_equal_oracle_head4096_clear"] == 1.0 and d["cpu_baseline"]["kind"] == "port"
+
+
+@pytest.mark.gpu
+def test_gpu_plain_line_is_the_headline_and_dumps_the_same_symbols(tmp_path):
+    """A plain N = 1 run: the contract fields, none of --full's legs, --steps timed steps; two runs with the same arguments
+    dump the same symbols of their last step, and they equal what the --full run's gate checks against the oracle."""
+    lines = []
+    for d in ("a", "b"):
+        lines.append(_one_line(_run(["--frames", "65536", "--steps", "3", "--warmup", "1", "--ramp-ms", "20",
+                                     "--dump-outputs", str(tmp_path / d)], {})))
+    d = lines[0]
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["ms_per_step"] > 0 and abs(d["value"] - 65536 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    assert d["gates_failed"] == [] and not {"roofline", "configs", "hello_world1", "receive", "cpu_baseline"} & set(d)
+    a, b = [np.load(tmp_path / x / "symbols.npy") for x in ("a", "b")]
+    assert a.dtype == np.float32 and a.shape == (65536,) and np.array_equal(a, b) and set(np.unique(a)) <= {0.0, 1.0, 255.0}
+    f = _one_line(_run(["--full", "--no-configs", "--no-hello1", "--no-receive", "--sustain-s", "0", "--no-live-traffic",
+                        "--frames", "65536", "--steps", "2", "--warmup", "1", "--ramp-ms", "20", "--dump-outputs", str(tmp_path / "f")], {}))
+    assert f["symbols_equal_oracle_head4096_clear"] == 1.0 and f["gates_failed"] == []
+    assert np.array_equal(np.load(tmp_path / "f" / "symbols.npy"), a)
 
 
 @pytest.mark.gpu
