@@ -1,0 +1,306 @@
+// uc_link_api.cpp -- the C-ABI of include/uchirp_link.h on top of uc_link_kernel.hip: errors, the link object and its
+// staging buffers, argument checks, the two launches.  No CPU compute path exists here: without a usable HIP device
+// uc_link_create fails.  Every entry point leaves the calling thread's current HIP device as it found it.
+#include <hip/hip_runtime.h>
+
+#include <cerrno>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+
+#include "../../include/uchirp_link.h"
+#include "uc_link.hpp"
+
+using namespace uc_link_dev;
+
+struct uc_link {
+  int device = 0;
+  uc_link_config cfg{};
+  int n_sym = 0;
+  int cus = 0;
+  unsigned grid_override = 0;      // UC_LINK_GRID under UC_TUNING=1
+  // staging: [n_streams Stream records][n_streams * text_stride bytes], pinned on the host and its twin on the device.
+  // Two such pairs, used in turn: call k stages while call k - 1's copy still waits in its stream, so that a loop of
+  // calls blocks the host only on the copy of two calls back.
+  struct Slot {
+    void* pinned = nullptr;
+    void* dev = nullptr;
+    size_t cap = 0;
+    hipEvent_t copied = nullptr;   // this slot's last host-to-device copy has read the pinned buffer
+    hipEvent_t done = nullptr;     // this slot's last kernel has read the device buffer
+    bool in_flight = false;
+  };
+  Slot slot[2];
+  unsigned next = 0;
+};
+
+namespace {
+
+thread_local std::string g_err;
+
+int fail(int code, const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof(buf), fmt, ap);
+  va_end(ap);
+  g_err = buf;
+  return code;
+}
+
+int hip_fail(hipError_t e, const char* what) { return fail(-EIO, "%s: %s", what, hipGetErrorString(e)); }
+
+// the calling thread's current device, put back when the entry point returns
+struct DeviceGuard {
+  int prev = -1;
+  DeviceGuard() {
+    if (hipGetDevice(&prev) != hipSuccess) {
+      prev = -1;
+      (void)hipGetLastError();
+    }
+  }
+  ~DeviceGuard() {
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+};
+
+bool is_device_ptr(const void* p) {
+  hipPointerAttribute_t attr;
+  memset(&attr, 0, sizeof(attr));
+  if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+    (void)hipGetLastError();  // clear the sticky "invalid value" of a plain host pointer
+    return false;
+  }
+  return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
+}
+
+size_t elem_size(int dtype) {
+  switch (dtype) {
+    case UC_LINK_DTYPE_I32:
+    case UC_LINK_DTYPE_F32: return 4;
+    case UC_LINK_DTYPE_I16: return 2;
+    default: return 0;
+  }
+}
+
+bool config_ok(const uc_link_config* c) {
+  if (!(c->fs_tx > 0.0) || !(c->t_symbol > 0.0) || !std::isfinite(c->fs_tx) || !std::isfinite(c->t_symbol)) return false;
+  if (!std::isfinite(c->f0) || !std::isfinite(c->f1)) return false;
+  const double n = c->t_symbol * c->fs_tx;
+  return n >= 2.0 && n < 1e9 && c->n_preamble < (1u << 20) && c->n_guard < (1u << 20);
+}
+
+// the slot's staging pair holds at least `bytes`; called before anything of the call is enqueued
+int reserve(uc_link::Slot* l, size_t bytes) {
+  if (bytes <= l->cap) return 0;
+  size_t cap = l->cap ? l->cap : 4096;
+  while (cap < bytes) cap *= 2;
+  void *p = nullptr, *d = nullptr;
+  hipError_t e = hipHostMalloc(&p, cap, hipHostMallocDefault);
+  if (e != hipSuccess) return fail(-ENOMEM, "uc_link_transmit: %zu bytes of pinned staging: %s", cap, hipGetErrorString(e));
+  e = hipMalloc(&d, cap);
+  if (e != hipSuccess) {
+    (void)hipHostFree(p);
+    return fail(-ENOMEM, "uc_link_transmit: %zu bytes of device staging: %s", cap, hipGetErrorString(e));
+  }
+  if (l->in_flight) (void)hipEventSynchronize(l->done);  // the old pair may still be read
+  if (l->pinned) (void)hipHostFree(l->pinned);
+  if (l->dev) (void)hipFree(l->dev);
+  l->pinned = p;
+  l->dev = d;
+  l->cap = cap;
+  l->in_flight = false;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int uc_link_abi_version(void) { return UC_LINK_ABI_VERSION; }
+
+const char* uc_link_last_error(void) { return g_err.c_str(); }
+
+int uc_link_default_config(uc_link_config* cfg) {
+  if (!cfg) return fail(-EINVAL, "uc_link_default_config: cfg is NULL");
+  memset(cfg, 0, sizeof(*cfg));
+  cfg->fs_tx = 44100.0;
+  cfg->t_symbol = 0.0262;
+  cfg->f0 = 16000.0;
+  cfg->f1 = 19000.0;
+  cfg->n_preamble = 7;
+  cfg->n_guard = 12;
+  return 0;
+}
+
+int uc_link_create(int device, const uc_link_config* cfg, uc_link** out) {
+  if (!out) return fail(-EINVAL, "uc_link_create: out is NULL");
+  *out = nullptr;
+  uc_link_config c;
+  if (cfg)
+    c = *cfg;
+  else
+    uc_link_default_config(&c);
+  if (!config_ok(&c)) return fail(-EINVAL, "uc_link_create: not a frame format (fs_tx, t_symbol > 0, at least 2 samples per symbol)");
+  int ndev = 0;
+  hipError_t e = hipGetDeviceCount(&ndev);
+  if (e != hipSuccess || ndev <= 0) {
+    (void)hipGetLastError();
+    return fail(-ENODEV, "uc_link_create: no HIP device (%s); this library has no CPU path",
+                e != hipSuccess ? hipGetErrorString(e) : "0 devices");
+  }
+  if (device < 0 || device >= ndev) return fail(-ENODEV, "uc_link_create: device %d out of range [0,%d)", device, ndev);
+  DeviceGuard guard;
+  if ((e = hipSetDevice(device)) != hipSuccess) return hip_fail(e, "uc_link_create: hipSetDevice");
+  hipDeviceProp_t prop;
+  if ((e = hipGetDeviceProperties(&prop, device)) != hipSuccess) return hip_fail(e, "uc_link_create: hipGetDeviceProperties");
+  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+    return fail(-ENODEV, "uc_link_create: device %d is %s; the kernels are built for gfx950 only", device, prop.gcnArchName);
+  uc_link* l = new uc_link();
+  l->device = device;
+  l->cfg = c;
+  l->n_sym = (int)(c.t_symbol * c.fs_tx);
+  l->cus = prop.multiProcessorCount;
+  // experiment switches are read only under UC_TUNING=1, so that a stray variable in a production environment changes nothing
+  const char* tuning = getenv("UC_TUNING");
+  if (tuning && !strcmp(tuning, "1")) {
+    const char* g = getenv("UC_LINK_GRID");
+    if (g && atoi(g) > 0) l->grid_override = (unsigned)atoi(g);
+  }
+  for (uc_link::Slot& sl : l->slot)
+    if ((e = hipEventCreateWithFlags(&sl.copied, hipEventDisableTiming)) != hipSuccess ||
+        (e = hipEventCreateWithFlags(&sl.done, hipEventDisableTiming)) != hipSuccess) {
+      uc_link_destroy(l);
+      return hip_fail(e, "uc_link_create: hipEventCreate");
+    }
+  *out = l;
+  return 0;
+}
+
+void uc_link_destroy(uc_link* l) {
+  if (!l) return;
+  DeviceGuard guard;
+  (void)hipSetDevice(l->device);
+  for (uc_link::Slot& sl : l->slot) {
+    if (sl.in_flight) (void)hipEventSynchronize(sl.done);
+    if (sl.pinned) (void)hipHostFree(sl.pinned);
+    if (sl.dev) (void)hipFree(sl.dev);
+    if (sl.copied) (void)hipEventDestroy(sl.copied);
+    if (sl.done) (void)hipEventDestroy(sl.done);
+  }
+  delete l;
+}
+
+int uc_link_transmit(uc_link* l, const uint8_t* text, size_t text_stride, const uc_link_stream* params, size_t n_streams,
+                     void* out_dev, int dtype, double fs_out, uint64_t first_sample, size_t n_samples, size_t stride_elems,
+                     uint64_t seed, void* hip_stream) {
+  // ---- checks: nothing is enqueued before the last of them
+  if (!l) return fail(-EINVAL, "uc_link_transmit: link is NULL");
+  if (!params || !out_dev) return fail(-EINVAL, "uc_link_transmit: params / out_dev is NULL");
+  if (n_streams == 0 || n_streams > 0xFFFFFFFFull) return fail(-EINVAL, "uc_link_transmit: n_streams %zu out of range", n_streams);
+  if (n_samples == 0) return fail(-EINVAL, "uc_link_transmit: n_samples is 0");
+  const size_t esz = elem_size(dtype);
+  if (!esz) return fail(-EINVAL, "uc_link_transmit: unknown dtype %d", dtype);
+  if (!(fs_out > 0.0) || !std::isfinite(fs_out)) return fail(-EINVAL, "uc_link_transmit: fs_out must be positive");
+  if (text_stride > UC_LINK_MAX_TEXT) return fail(-EINVAL, "uc_link_transmit: text_stride %zu > %d", text_stride, UC_LINK_MAX_TEXT);
+  const size_t stride = stride_elems ? stride_elems : n_samples;
+  if (stride < n_samples) return fail(-EINVAL, "uc_link_transmit: stride_elems %zu < n_samples %zu", stride_elems, n_samples);
+  if (first_sample > (1ull << 52) || n_samples > (1ull << 40)) return fail(-EINVAL, "uc_link_transmit: sample range too large");
+  bool any_text = false;
+  for (size_t s = 0; s < n_streams; ++s) {
+    const uc_link_stream& q = params[s];
+    if (q.text_len > text_stride)
+      return fail(-EINVAL, "uc_link_transmit: stream %zu: text_len %u > text_stride %zu", s, q.text_len, text_stride);
+    if (!std::isfinite(q.lead_samples) || !std::isfinite(q.amplitude) || !std::isfinite(q.sigma) || !std::isfinite(q.ppm) || q.sigma < 0.0f)
+      return fail(-EINVAL, "uc_link_transmit: stream %zu: parameters must be finite, sigma >= 0", s);
+    any_text |= q.text_len != 0;
+  }
+  if (any_text && !text) return fail(-EINVAL, "uc_link_transmit: text is NULL");
+  DeviceGuard guard;
+  hipError_t e = hipSetDevice(l->device);
+  if (e != hipSuccess) return hip_fail(e, "uc_link_transmit: hipSetDevice");
+  if (!is_device_ptr(out_dev)) return fail(-EINVAL, "uc_link_transmit: out_dev is not device memory");
+  const uint64_t first_quad = first_sample / 4, end_quad = (first_sample + n_samples + 3) / 4;
+  const uint64_t tiles_per_stream = (end_quad - first_quad + TILE_QUADS - 1) / TILE_QUADS;
+  const size_t rec_bytes = n_streams * sizeof(Stream);
+  const size_t bytes = rec_bytes + n_streams * text_stride;
+  uc_link::Slot& sl = l->slot[l->next];
+  int rc = reserve(&sl, bytes);
+  if (rc) return rc;
+
+  // ---- stage (this slot's pinned buffer is free once the copy of two calls back has run)
+  if (sl.in_flight) (void)hipEventSynchronize(sl.copied);
+  Stream* rec = (Stream*)sl.pinned;
+  for (size_t s = 0; s < n_streams; ++s) {
+    const uc_link_stream& q = params[s];
+    rec[s].rate = (1.0 / fs_out) * (1.0 + (double)q.ppm * 1e-6);
+    rec[s].lead_s = q.lead_samples / fs_out;
+    rec[s].amp = (float)((double)q.amplitude * 1.4142135623730951);
+    rec[s].sigma = q.sigma;
+    rec[s].text_len = q.text_len;
+    rec[s].pad = 0;
+  }
+  if (text_stride) {
+    if (text)
+      memcpy((char*)sl.pinned + rec_bytes, text, n_streams * text_stride);
+    else
+      memset((char*)sl.pinned + rec_bytes, 0, n_streams * text_stride);
+  }
+  Params p;
+  memset(&p, 0, sizeof(p));
+  const uc_link_config& c = l->cfg;
+  p.sym_dur = (double)l->n_sym / c.fs_tx;
+  p.inv_sym_dur = 1.0 / p.sym_dur;
+  p.t_scale = c.fs_tx * c.t_symbol / (double)(l->n_sym - 1);
+  p.f0 = c.f0;
+  p.f1 = c.f1;
+  p.half_k = (c.f1 - c.f0) / c.t_symbol / 2.0;
+  p.first_sample = first_sample;
+  p.n_samples = n_samples;
+  p.stride = stride;
+  p.seed = seed;
+  p.first_quad = first_quad;
+  p.tiles_per_stream = (uint32_t)tiles_per_stream;
+  p.n_preamble = c.n_preamble;
+  p.text_stride = (uint32_t)text_stride;
+  p.n_streams = (uint32_t)n_streams;
+  const uint64_t n_tiles = (uint64_t)n_streams * tiles_per_stream;
+  uint64_t grid = (uint64_t)l->cus * 8;       // 8 workgroups of 4 waves per CU: every wave slot of the chip
+  if (l->grid_override) grid = l->grid_override;
+  if (grid > n_tiles) grid = n_tiles;
+
+  // ---- enqueue
+  hipStream_t hs = (hipStream_t)hip_stream;
+  if (sl.in_flight && (e = hipStreamWaitEvent(hs, sl.done, 0)) != hipSuccess) return hip_fail(e, "uc_link_transmit: hipStreamWaitEvent");
+  if ((e = hipMemcpyAsync(sl.dev, sl.pinned, bytes, hipMemcpyHostToDevice, hs)) != hipSuccess)
+    return hip_fail(e, "uc_link_transmit: hipMemcpyAsync");
+  (void)hipEventRecord(sl.copied, hs);
+  e = (hipError_t)launch_transmit(dtype, (unsigned)grid, hs, p, (const Stream*)sl.dev, (const uint8_t*)sl.dev + rec_bytes, out_dev);
+  (void)hipEventRecord(sl.done, hs);
+  sl.in_flight = true;
+  l->next ^= 1u;
+  if (e != hipSuccess) return hip_fail(e, "uc_link_transmit: launch");
+  return 0;
+}
+
+int uc_link_noise_words(uc_link* l, uint64_t seed, uint64_t stream, uint64_t first_counter, size_t n_counters, uint32_t* out_dev,
+                        void* hip_stream) {
+  if (!l) return fail(-EINVAL, "uc_link_noise_words: link is NULL");
+  if (!out_dev) return fail(-EINVAL, "uc_link_noise_words: out_dev is NULL");
+  if (n_counters == 0 || n_counters > (1ull << 40)) return fail(-EINVAL, "uc_link_noise_words: n_counters %zu out of range", n_counters);
+  DeviceGuard guard;
+  hipError_t e = hipSetDevice(l->device);
+  if (e != hipSuccess) return hip_fail(e, "uc_link_noise_words: hipSetDevice");
+  if (!is_device_ptr(out_dev)) return fail(-EINVAL, "uc_link_noise_words: out_dev is not device memory");
+  uint64_t grid = (n_counters + THREADS - 1) / THREADS;
+  const uint64_t cap = (uint64_t)l->cus * 8;
+  if (grid > cap) grid = cap;
+  e = (hipError_t)launch_words((unsigned)grid, hip_stream, seed, stream, first_counter, n_counters, out_dev);
+  if (e != hipSuccess) return hip_fail(e, "uc_link_noise_words: launch");
+  return 0;
+}
+
+}  // extern "C"
