@@ -1,18 +1,9 @@
 // uc_link_api.cpp -- the C-ABI of include/uchirp_link.h on top of uc_link_kernel.hip: errors, the link object and its
 // staging buffers, argument checks, the two launches.  No CPU compute path exists here: without a usable HIP device
 // uc_link_create fails.  Every entry point leaves the calling thread's current HIP device as it found it.
-#include <hip/hip_runtime.h>
-
-#include <cerrno>
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-
 #include "../../include/uchirp_link.h"
 #include "uc_link.hpp"
+#include "uc_link_host.hpp"
 
 using namespace uc_link_dev;
 
@@ -25,98 +16,9 @@ struct uc_link {
   // staging: [n_streams Stream records][n_streams * text_stride bytes], pinned on the host and its twin on the device.
   // Two such pairs, used in turn: call k stages while call k - 1's copy still waits in its stream, so that a loop of
   // calls blocks the host only on the copy of two calls back.
-  struct Slot {
-    void* pinned = nullptr;
-    void* dev = nullptr;
-    size_t cap = 0;
-    hipEvent_t copied = nullptr;   // this slot's last host-to-device copy has read the pinned buffer
-    hipEvent_t done = nullptr;     // this slot's last kernel has read the device buffer
-    bool in_flight = false;
-  };
-  Slot slot[2];
+  StagingSlot slot[2];
   unsigned next = 0;
 };
-
-namespace {
-
-thread_local std::string g_err;
-
-int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  g_err = buf;
-  return code;
-}
-
-int hip_fail(hipError_t e, const char* what) { return fail(-EIO, "%s: %s", what, hipGetErrorString(e)); }
-
-// the calling thread's current device, put back when the entry point returns
-struct DeviceGuard {
-  int prev = -1;
-  DeviceGuard() {
-    if (hipGetDevice(&prev) != hipSuccess) {
-      prev = -1;
-      (void)hipGetLastError();
-    }
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-
-bool is_device_ptr(const void* p) {
-  hipPointerAttribute_t attr;
-  memset(&attr, 0, sizeof(attr));
-  if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-    (void)hipGetLastError();  // clear the sticky "invalid value" of a plain host pointer
-    return false;
-  }
-  return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
-}
-
-size_t elem_size(int dtype) {
-  switch (dtype) {
-    case UC_LINK_DTYPE_I32:
-    case UC_LINK_DTYPE_F32: return 4;
-    case UC_LINK_DTYPE_I16: return 2;
-    default: return 0;
-  }
-}
-
-bool config_ok(const uc_link_config* c) {
-  if (!(c->fs_tx > 0.0) || !(c->t_symbol > 0.0) || !std::isfinite(c->fs_tx) || !std::isfinite(c->t_symbol)) return false;
-  if (!std::isfinite(c->f0) || !std::isfinite(c->f1)) return false;
-  const double n = c->t_symbol * c->fs_tx;
-  return n >= 2.0 && n < 1e9 && c->n_preamble < (1u << 20) && c->n_guard < (1u << 20);
-}
-
-// the slot's staging pair holds at least `bytes`; called before anything of the call is enqueued
-int reserve(uc_link::Slot* l, size_t bytes) {
-  if (bytes <= l->cap) return 0;
-  size_t cap = l->cap ? l->cap : 4096;
-  while (cap < bytes) cap *= 2;
-  void *p = nullptr, *d = nullptr;
-  hipError_t e = hipHostMalloc(&p, cap, hipHostMallocDefault);
-  if (e != hipSuccess) return fail(-ENOMEM, "uc_link_transmit: %zu bytes of pinned staging: %s", cap, hipGetErrorString(e));
-  e = hipMalloc(&d, cap);
-  if (e != hipSuccess) {
-    (void)hipHostFree(p);
-    return fail(-ENOMEM, "uc_link_transmit: %zu bytes of device staging: %s", cap, hipGetErrorString(e));
-  }
-  if (l->in_flight) (void)hipEventSynchronize(l->done);  // the old pair may still be read
-  if (l->pinned) (void)hipHostFree(l->pinned);
-  if (l->dev) (void)hipFree(l->dev);
-  l->pinned = p;
-  l->dev = d;
-  l->cap = cap;
-  l->in_flight = false;
-  return 0;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -126,13 +28,7 @@ const char* uc_link_last_error(void) { return g_err.c_str(); }
 
 int uc_link_default_config(uc_link_config* cfg) {
   if (!cfg) return fail(-EINVAL, "uc_link_default_config: cfg is NULL");
-  memset(cfg, 0, sizeof(*cfg));
-  cfg->fs_tx = 44100.0;
-  cfg->t_symbol = 0.0262;
-  cfg->f0 = 16000.0;
-  cfg->f1 = 19000.0;
-  cfg->n_preamble = 7;
-  cfg->n_guard = 12;
+  reference_config(cfg);
   return 0;
 }
 
@@ -170,7 +66,7 @@ int uc_link_create(int device, const uc_link_config* cfg, uc_link** out) {
     const char* g = getenv("UC_LINK_GRID");
     if (g && atoi(g) > 0) l->grid_override = (unsigned)atoi(g);
   }
-  for (uc_link::Slot& sl : l->slot)
+  for (StagingSlot& sl : l->slot)
     if ((e = hipEventCreateWithFlags(&sl.copied, hipEventDisableTiming)) != hipSuccess ||
         (e = hipEventCreateWithFlags(&sl.done, hipEventDisableTiming)) != hipSuccess) {
       uc_link_destroy(l);
@@ -184,7 +80,7 @@ void uc_link_destroy(uc_link* l) {
   if (!l) return;
   DeviceGuard guard;
   (void)hipSetDevice(l->device);
-  for (uc_link::Slot& sl : l->slot) {
+  for (StagingSlot& sl : l->slot) {
     if (sl.in_flight) (void)hipEventSynchronize(sl.done);
     if (sl.pinned) (void)hipHostFree(sl.pinned);
     if (sl.dev) (void)hipFree(sl.dev);
@@ -227,8 +123,8 @@ int uc_link_transmit(uc_link* l, const uint8_t* text, size_t text_stride, const 
   const uint64_t tiles_per_stream = (end_quad - first_quad + TILE_QUADS - 1) / TILE_QUADS;
   const size_t rec_bytes = n_streams * sizeof(Stream);
   const size_t bytes = rec_bytes + n_streams * text_stride;
-  uc_link::Slot& sl = l->slot[l->next];
-  int rc = reserve(&sl, bytes);
+  StagingSlot& sl = l->slot[l->next];
+  int rc = reserve(&sl, bytes, "uc_link_transmit");
   if (rc) return rc;
 
   // ---- stage (this slot's pinned buffer is free once the copy of two calls back has run)

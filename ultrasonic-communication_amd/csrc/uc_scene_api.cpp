@@ -1,0 +1,219 @@
+// uc_scene_api.cpp -- the C-ABI of include/uchirp_scene.h on top of uc_scene_kernel.hip: errors, the scene object and
+// its staging buffers, argument checks, the launch.  Built like uc_link_api.cpp and sharing nothing with it at link time:
+// libuchirp_scene.so stands alone.  No CPU compute path exists here: without a usable HIP device uc_scene_create fails.
+// Every entry point leaves the calling thread's current HIP device as it found it.
+#include "../../include/uchirp_scene.h"
+#include "uc_link_host.hpp"
+#include "uc_scene.hpp"
+
+using namespace uc_scene_dev;
+
+struct uc_scene {
+  int device = 0;
+  uc_link_config cfg{};
+  int n_sym = 0;
+  int cus = 0;
+  unsigned grid_override = 0;      // UC_SCENE_GRID under UC_TUNING=1
+  int resident[4] = {0, 0, 0, 0};  // by dtype: workgroups one CU holds at once (asked once per format)
+  // staging: [n_paths Path records][n_mics Mic records][n_tx * text_stride bytes], pinned on the host and its twin on the device.
+  // Two such pairs, used in turn: call k stages while call k - 1's copy still waits in its stream, so that a loop of
+  // calls blocks the host only on the copy of two calls back.
+  StagingSlot slot[2];
+  unsigned next = 0;
+};
+
+extern "C" {
+
+int uc_scene_abi_version(void) { return UC_SCENE_ABI_VERSION; }
+
+const char* uc_scene_last_error(void) { return g_err.c_str(); }
+
+int uc_scene_default_config(uc_link_config* cfg) {
+  if (!cfg) return fail(-EINVAL, "uc_scene_default_config: cfg is NULL");
+  reference_config(cfg);
+  return 0;
+}
+
+int uc_scene_create(int device, const uc_link_config* cfg, uc_scene** out) {
+  if (!out) return fail(-EINVAL, "uc_scene_create: out is NULL");
+  *out = nullptr;
+  uc_link_config c;
+  if (cfg)
+    c = *cfg;
+  else
+    uc_scene_default_config(&c);
+  if (!config_ok(&c)) return fail(-EINVAL, "uc_scene_create: not a frame format (fs_tx, t_symbol > 0, at least 2 samples per symbol)");
+  int ndev = 0;
+  hipError_t e = hipGetDeviceCount(&ndev);
+  if (e != hipSuccess || ndev <= 0) {
+    (void)hipGetLastError();
+    return fail(-ENODEV, "uc_scene_create: no HIP device (%s); this library has no CPU path",
+                e != hipSuccess ? hipGetErrorString(e) : "0 devices");
+  }
+  if (device < 0 || device >= ndev) return fail(-ENODEV, "uc_scene_create: device %d out of range [0,%d)", device, ndev);
+  DeviceGuard guard;
+  if ((e = hipSetDevice(device)) != hipSuccess) return hip_fail(e, "uc_scene_create: hipSetDevice");
+  hipDeviceProp_t prop;
+  if ((e = hipGetDeviceProperties(&prop, device)) != hipSuccess) return hip_fail(e, "uc_scene_create: hipGetDeviceProperties");
+  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+    return fail(-ENODEV, "uc_scene_create: device %d is %s; the kernels are built for gfx950 only", device, prop.gcnArchName);
+  uc_scene* l = new uc_scene();
+  l->device = device;
+  l->cfg = c;
+  l->n_sym = (int)(c.t_symbol * c.fs_tx);
+  l->cus = prop.multiProcessorCount;
+  // experiment switches are read only under UC_TUNING=1, so that a stray variable in a production environment changes nothing
+  const char* tuning = getenv("UC_TUNING");
+  if (tuning && !strcmp(tuning, "1")) {
+    const char* g = getenv("UC_SCENE_GRID");
+    if (g && atoi(g) > 0) l->grid_override = (unsigned)atoi(g);
+  }
+  for (StagingSlot& sl : l->slot)
+    if ((e = hipEventCreateWithFlags(&sl.copied, hipEventDisableTiming)) != hipSuccess ||
+        (e = hipEventCreateWithFlags(&sl.done, hipEventDisableTiming)) != hipSuccess) {
+      uc_scene_destroy(l);
+      return hip_fail(e, "uc_scene_create: hipEventCreate");
+    }
+  *out = l;
+  return 0;
+}
+
+void uc_scene_destroy(uc_scene* l) {
+  if (!l) return;
+  DeviceGuard guard;
+  (void)hipSetDevice(l->device);
+  for (StagingSlot& sl : l->slot) {
+    if (sl.in_flight) (void)hipEventSynchronize(sl.done);
+    if (sl.pinned) (void)hipHostFree(sl.pinned);
+    if (sl.dev) (void)hipFree(sl.dev);
+    if (sl.copied) (void)hipEventDestroy(sl.copied);
+    if (sl.done) (void)hipEventDestroy(sl.done);
+  }
+  delete l;
+}
+
+int uc_scene_render(uc_scene* l, const uint8_t* text, size_t text_stride, const uint32_t* text_len, size_t n_tx,
+                    const uc_scene_path* paths, size_t n_paths, const uc_scene_mic* mics, size_t n_mics, void* out_dev, int dtype,
+                    double fs_out, uint64_t first_sample, size_t n_samples, size_t stride_elems, uint64_t seed, void* hip_stream) {
+  // ---- checks: nothing is enqueued before the last of them
+  if (!l) return fail(-EINVAL, "uc_scene_render: scene is NULL");
+  if (!out_dev) return fail(-EINVAL, "uc_scene_render: out_dev is NULL");
+  if (n_mics == 0 || n_mics > 0xFFFFFFFFull) return fail(-EINVAL, "uc_scene_render: n_mics %zu out of range", n_mics);
+  if (n_paths > 0xFFFFFFFFull || n_tx > 0xFFFFFFFFull) return fail(-EINVAL, "uc_scene_render: n_paths / n_tx out of range");
+  if (!mics) return fail(-EINVAL, "uc_scene_render: mics is NULL");
+  if (n_paths && !paths) return fail(-EINVAL, "uc_scene_render: paths is NULL, n_paths %zu", n_paths);
+  if (n_tx && !text_len) return fail(-EINVAL, "uc_scene_render: text_len is NULL, n_tx %zu", n_tx);
+  if (n_samples == 0) return fail(-EINVAL, "uc_scene_render: n_samples is 0");
+  const size_t esz = elem_size(dtype);
+  if (!esz) return fail(-EINVAL, "uc_scene_render: unknown dtype %d", dtype);
+  if (!(fs_out > 0.0) || !std::isfinite(fs_out)) return fail(-EINVAL, "uc_scene_render: fs_out must be positive");
+  if (text_stride > UC_LINK_MAX_TEXT) return fail(-EINVAL, "uc_scene_render: text_stride %zu > %d", text_stride, UC_LINK_MAX_TEXT);
+  const size_t stride = stride_elems ? stride_elems : n_samples;
+  if (stride < n_samples) return fail(-EINVAL, "uc_scene_render: stride_elems %zu < n_samples %zu", stride_elems, n_samples);
+  if (first_sample > (1ull << 52) || n_samples > (1ull << 40)) return fail(-EINVAL, "uc_scene_render: sample range too large");
+  bool any_text = false;
+  for (size_t t = 0; t < n_tx; ++t) {
+    if (text_len[t] > text_stride)
+      return fail(-EINVAL, "uc_scene_render: transmission %zu: text_len %u > text_stride %zu", t, text_len[t], text_stride);
+    any_text |= text_len[t] != 0;
+  }
+  if (any_text && !text) return fail(-EINVAL, "uc_scene_render: text is NULL");
+  for (size_t k = 0; k < n_paths; ++k) {
+    const uc_scene_path& q = paths[k];
+    if (q.tx >= n_tx) return fail(-EINVAL, "uc_scene_render: path %zu: tx %u >= n_tx %zu", k, q.tx, n_tx);
+    if (!std::isfinite(q.lead_samples) || !std::isfinite(q.gain) || !std::isfinite(q.ppm))
+      return fail(-EINVAL, "uc_scene_render: path %zu: lead_samples, gain and ppm must be finite", k);
+  }
+  for (size_t m = 0; m < n_mics; ++m) {
+    const uc_scene_mic& q = mics[m];
+    if (q.n_paths > UC_SCENE_MAX_PATHS)
+      return fail(-EINVAL, "uc_scene_render: microphone %zu: n_paths %u > %d", m, q.n_paths, UC_SCENE_MAX_PATHS);
+    if ((uint64_t)q.first_path + q.n_paths > n_paths)
+      return fail(-EINVAL, "uc_scene_render: microphone %zu: paths [%u, %u + %u) beyond n_paths %zu", m, q.first_path, q.first_path,
+                  q.n_paths, n_paths);
+    if (!std::isfinite(q.sigma) || q.sigma < 0.0f) return fail(-EINVAL, "uc_scene_render: microphone %zu: sigma must be finite and >= 0", m);
+  }
+  DeviceGuard guard;
+  hipError_t e = hipSetDevice(l->device);
+  if (e != hipSuccess) return hip_fail(e, "uc_scene_render: hipSetDevice");
+  if (!is_device_ptr(out_dev)) return fail(-EINVAL, "uc_scene_render: out_dev is not device memory");
+  const uint64_t first_quad = first_sample / 4, end_quad = (first_sample + n_samples + 3) / 4;
+  const uint64_t tiles_per_mic = (end_quad - first_quad + TILE_QUADS - 1) / TILE_QUADS;
+  const size_t path_bytes = n_paths * sizeof(Path), mic_bytes = n_mics * sizeof(Mic);
+  const size_t bytes = path_bytes + mic_bytes + n_tx * text_stride;
+  StagingSlot& sl = l->slot[l->next];
+  int rc = reserve(&sl, bytes, "uc_scene_render");
+  if (rc) return rc;
+
+  // ---- stage (this slot's pinned buffer is free once the copy of two calls back has run)
+  if (sl.in_flight) (void)hipEventSynchronize(sl.copied);
+  const uc_link_config& c = l->cfg;
+  Path* prec = (Path*)sl.pinned;
+  for (size_t k = 0; k < n_paths; ++k) {
+    const uc_scene_path& q = paths[k];
+    prec[k].rate = (1.0 / fs_out) * (1.0 + (double)q.ppm * 1e-6);
+    prec[k].lead_s = q.lead_samples / fs_out;
+    prec[k].amp = (float)((double)q.gain * 1.4142135623730951);
+    prec[k].n_on = 2u + c.n_preamble + 8u * text_len[q.tx];
+    prec[k].tx = q.tx;
+    prec[k].pad = 0;
+  }
+  Mic* mrec = (Mic*)((char*)sl.pinned + path_bytes);
+  for (size_t m = 0; m < n_mics; ++m) {
+    mrec[m].first_path = mics[m].first_path;
+    mrec[m].n_paths = mics[m].n_paths;
+    mrec[m].sigma = mics[m].sigma;
+    mrec[m].pad = 0;
+  }
+  if (n_tx * text_stride) {
+    if (text)
+      memcpy((char*)sl.pinned + path_bytes + mic_bytes, text, n_tx * text_stride);
+    else
+      memset((char*)sl.pinned + path_bytes + mic_bytes, 0, n_tx * text_stride);
+  }
+  Params p;
+  memset(&p, 0, sizeof(p));
+  p.sym_dur = (double)l->n_sym / c.fs_tx;
+  p.inv_sym_dur = 1.0 / p.sym_dur;
+  p.t_scale = c.fs_tx * c.t_symbol / (double)(l->n_sym - 1);
+  p.f0 = c.f0;
+  p.f1 = c.f1;
+  p.half_k = (c.f1 - c.f0) / c.t_symbol / 2.0;
+  p.first_sample = first_sample;
+  p.n_samples = n_samples;
+  p.stride = stride;
+  p.seed = seed;
+  p.first_quad = first_quad;
+  p.tiles_per_stream = (uint32_t)tiles_per_mic;
+  p.n_preamble = c.n_preamble;
+  p.text_stride = (uint32_t)text_stride;
+  p.n_streams = (uint32_t)n_mics;
+  const uint64_t n_tiles = (uint64_t)n_mics * tiles_per_mic;
+  // a persistent grid of exactly the workgroups the chip holds at once: the tiles are dealt statically, so a workgroup
+  // that had to wait for a slot would run its whole share alone after the others.  The scene kernels' scalar registers
+  // leave 7 workgroups of 4 waves per CU where the link kernel has 8; the runtime's figure is asked, not assumed.
+  if (!l->resident[dtype]) {
+    const int r = resident_blocks_per_cu(dtype);
+    l->resident[dtype] = r > 0 ? r : 7;
+  }
+  uint64_t grid = (uint64_t)l->cus * (uint64_t)l->resident[dtype];
+  if (l->grid_override) grid = l->grid_override;
+  if (grid > n_tiles) grid = n_tiles;
+
+  // ---- enqueue
+  hipStream_t hs = (hipStream_t)hip_stream;
+  if (sl.in_flight && (e = hipStreamWaitEvent(hs, sl.done, 0)) != hipSuccess) return hip_fail(e, "uc_scene_render: hipStreamWaitEvent");
+  if ((e = hipMemcpyAsync(sl.dev, sl.pinned, bytes, hipMemcpyHostToDevice, hs)) != hipSuccess)
+    return hip_fail(e, "uc_scene_render: hipMemcpyAsync");
+  (void)hipEventRecord(sl.copied, hs);
+  const char* d = (const char*)sl.dev;
+  e = (hipError_t)launch_render(dtype, (unsigned)grid, hs, p, (const Mic*)(d + path_bytes), (const Path*)d,
+                                (const uint8_t*)(d + path_bytes + mic_bytes), out_dev);
+  (void)hipEventRecord(sl.done, hs);
+  sl.in_flight = true;
+  l->next ^= 1u;
+  if (e != hipSuccess) return hip_fail(e, "uc_scene_render: launch");
+  return 0;
+}
+
+}  // extern "C"
