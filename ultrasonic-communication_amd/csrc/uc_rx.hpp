@@ -86,10 +86,11 @@ struct RxParams {
   uint32_t need_force;   // pricing runs only (UC_TUNING=1 UC_RX_NEED_FORCE): bit 31 set = every stream's word is the low 9 bits of this
 };
 
-// (shared by the replay kernels, uc_rx_state_reset and the CPU harness that ties it to main()'s switch: tests/cpp/san_host.cpp)
+// (shared by the replay kernels, uc_rx_state_reset and the CPU harness that ties it to main()'s switch: tests/cpp/need_check.cpp)
 // what the switch can still look at of a stream's NEXT block (uc_rx.hpp: RxParams::need).  FIFO offsets are counted in steps
 // of 256 samples: k = pos / 256 = 0 .. 16; the next block's NEW offsets are k = 9 .. 16 (bit k - 9); one block later they sit at
 // k - 8 = 1 .. 8, two blocks later only k = 16 is left (at 0).
+// Every word must hold offset m = 7 or m = 8: (w & 0xC0) != 0 is required by the ROWS save path (rows_masks / save7 in uc_band_kernel.hip).
 UC_HD inline uint32_t need_word(int state, uint32_t turn, uint32_t sync_position) {
   if (state == UC_STATE_IDLE) return turn ? 0x0ADu : 0x052u;  // acquisition: k = 4 + turn + 2 i now, the other set next block
   if (state == UC_STATE_SYNCHRONIZING) return 0x1FFu;         // may lock onto any of the eight positions: everything
