@@ -3,7 +3,8 @@
 # this pool and are not attempted).  What is instrumented: every host translation unit of libuchirp.so -- csrc/uc_api_*.cpp
 # (staging buffers, counter rings, graph slots, receive paths: argument checks and everything in front of the first device
 # call), csrc/uc_tables.cpp (reference tables, sinc^5 byte tables), csrc/uc_group.cpp (partition / span arithmetic, argument
-# checks, RCCL loading) -- the oracle, the loop-back RCCL stand-in, and a C++ harness (tests/cpp/san_host.cpp) that drives
+# checks, RCCL loading) -- csrc/uc_array_api.cpp of libuchirp_array.so (coefficients, argument checks) -- the oracle, the
+# loop-back RCCL stand-in, and a C++ harness (tests/cpp/san_host.cpp) that drives
 # include/uchirp_mainloop.hpp with a CPU dsp(), the table builders and the span functions over random and edge inputs.
 # The kernels' objects are linked in as they are (device code cannot be sanitized here).
 #   bash tools/sanitize.sh [log=profiles/rXX_sanitize.txt]      (also: make -C ultrasonic-communication_amd sanitize)
@@ -28,6 +29,10 @@ for f in uc_api_core uc_api_rx uc_api_stream uc_api_cic uc_api_clock uc_tables u
 done
 KOBJ="$(ls "$PKG"/csrc/*_kernel.o "$PKG"/csrc/*_kernel.clk.o)"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $SAN -o "$B/libuchirp.so" "$B"/uc_api_core.o "$B"/uc_api_rx.o "$B"/uc_api_stream.o "$B"/uc_api_cic.o "$B"/uc_api_clock.o "$B"/uc_tables.o "$B"/uc_group.o $KOBJ -ldl
+# the array combiner's host translation unit (argument checks, coefficients, staging arithmetic) against its kernel object
+make -C "$PKG" libuchirp_array.so > /dev/null
+/opt/rocm/bin/hipcc -std=c++17 -fPIC -Wall -Wextra -Wno-unused-parameter -ffp-contract=off -Wno-option-ignored $SAN -c "$PKG/csrc/uc_array_api.cpp" -o "$B/uc_array_api.o"
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $SAN -o "$B/libuchirp_array.so" "$B/uc_array_api.o" "$PKG/csrc/uc_array_kernel.o"
 $LLVM/clang -std=gnu11 -fPIC -Wall -Wextra -ffp-contract=off -march=x86-64-v3 $SAN -shared -o "$B/libuc_oracle.so" "$ROOT/oracle/uc_oracle.c" -lm
 $LLVM/clang++ -std=c++17 -fPIC -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include $SAN -shared -o "$B/libloopback_rccl.so" \
    "$ROOT/tests/stubs/loopback_rccl.cpp" -L/opt/rocm/lib -lamdhip64 -lrt
@@ -42,8 +47,8 @@ UC_TUNING=1 UC_RCCL_LIB="$B/libloopback_rccl.so" "$B/san_host"
 echo "== 1b. the need words of the live receivers against main()'s switch (tests/cpp/need_check.cpp)"
 "$B/need_check"
 echo "== 2. the CPU test files against the instrumented libraries (UCHIRP_LIB / UCO_LIB), ASan runtime preloaded into python"
-LD_PRELOAD="$RT" UCHIRP_LIB="$B/libuchirp.so" UCO_LIB="$B/libuc_oracle.so"\
-  python -m pytest "$ROOT/tests/test_group_cpu.py" "$ROOT/tests/test_oracle_golden.py" "$ROOT/tests/test_abi.py" \
+LD_PRELOAD="$RT" UCHIRP_LIB="$B/libuchirp.so" UCO_LIB="$B/libuc_oracle.so" UCHIRP_ARRAY_LIB="$B/libuchirp_array.so"\
+  python -m pytest "$ROOT/tests/test_array_cpu.py" "$ROOT/tests/test_group_cpu.py" "$ROOT/tests/test_oracle_golden.py" "$ROOT/tests/test_abi.py" \
   "$ROOT/tests/test_shard_gloo.py" "$ROOT/tests/test_dfsdm.py" -q -m "not gpu" -p no:cacheprovider -x 2>&1 | grep -v "^  File" | tail -25
 echo "== clean: no AddressSanitizer / UndefinedBehaviorSanitizer report in any step"
 } 2>&1 | tee "$LOG"
