@@ -1,5 +1,5 @@
 // uc_host.hpp -- host-side helpers that the C-ABI files of libuchirp_link.so (uc_link_api.cpp), libuchirp_scene.so
-// (uc_scene_api.cpp) and libuchirp_array.so (uc_array_api.cpp) share, so that their contracts cannot drift apart: the
+// (uc_scene_api.cpp), libuchirp_array.so (uc_array_api.cpp) and libuchirp_align.so (uc_align_api.cpp) share, so that their contracts cannot drift apart: the
 // thread's last error, the guard that restores the caller's HIP device, the test for device memory and the pinned + device
 // staging pair.  Nothing here knows a frame format (that part: uc_link_host.hpp).  Header-only and in an anonymous
 // namespace: every library gets its own copy (its own last error) and no symbol crosses a library boundary.
