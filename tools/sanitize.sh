@@ -3,7 +3,8 @@
 # this pool and are not attempted).  What is instrumented: every host translation unit of libuchirp.so -- csrc/uc_api_*.cpp
 # (staging buffers, counter rings, graph slots, receive paths: argument checks and everything in front of the first device
 # call), csrc/uc_tables.cpp (reference tables, sinc^5 byte tables), csrc/uc_group.cpp (partition / span arithmetic, argument
-# checks, RCCL loading) -- csrc/uc_array_api.cpp of libuchirp_array.so (coefficients, argument checks) -- the oracle, the
+# checks, RCCL loading) -- csrc/uc_array_api.cpp of libuchirp_array.so (coefficients, argument checks) -- csrc/uc_xcorr_api.cpp of
+# libuchirp_xcorr.so (peak rule, argument checks; a stand-alone program drives it) -- the oracle, the
 # loop-back RCCL stand-in, and a C++ harness (tests/cpp/san_host.cpp) that drives
 # include/uchirp_mainloop.hpp with a CPU dsp(), the table builders and the span functions over random and edge inputs.
 # The kernels' objects are linked in as they are (device code cannot be sanitized here).
@@ -33,6 +34,12 @@ KOBJ="$(ls "$PKG"/csrc/*_kernel.o "$PKG"/csrc/*_kernel.clk.o)"
 make -C "$PKG" libuchirp_array.so > /dev/null
 /opt/rocm/bin/hipcc -std=c++17 -fPIC -Wall -Wextra -Wno-unused-parameter -ffp-contract=off -Wno-option-ignored $SAN -c "$PKG/csrc/uc_array_api.cpp" -o "$B/uc_array_api.o"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $SAN -o "$B/libuchirp_array.so" "$B/uc_array_api.o" "$PKG/csrc/uc_array_kernel.o"
+# the wide-lag correlator's host translation unit (peak rule, argument checks) against its kernel object, driven by a
+# stand-alone program (tests/cpp/san_xcorr.cpp)
+make -C "$PKG" libuchirp_xcorr.so > /dev/null
+/opt/rocm/bin/hipcc -std=c++17 -fPIC -Wall -Wextra -Wno-unused-parameter -ffp-contract=off -Wno-option-ignored $SAN -c "$PKG/csrc/uc_xcorr_api.cpp" -o "$B/uc_xcorr_api.o"
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $SAN -o "$B/libuchirp_xcorr.so" "$B/uc_xcorr_api.o" "$PKG/csrc/uc_xcorr_kernel.o"
+$LLVM/clang++ -std=c++17 -I"$ROOT/include" $SAN -o "$B/san_xcorr" "$ROOT/tests/cpp/san_xcorr.cpp" -L"$B" -luchirp_xcorr -Wl,-rpath,"$B" -Wl,-rpath,"$(dirname "$RT")"
 $LLVM/clang -std=gnu11 -fPIC -Wall -Wextra -ffp-contract=off -march=x86-64-v3 $SAN -shared -o "$B/libuc_oracle.so" "$ROOT/oracle/uc_oracle.c" -lm
 $LLVM/clang++ -std=c++17 -fPIC -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include $SAN -shared -o "$B/libloopback_rccl.so" \
    "$ROOT/tests/stubs/loopback_rccl.cpp" -L/opt/rocm/lib -lamdhip64 -lrt
@@ -46,6 +53,8 @@ echo "== 1. C++ harness (mainloop header with a CPU dsp(), table builders, parti
 UC_TUNING=1 UC_RCCL_LIB="$B/libloopback_rccl.so" "$B/san_host"
 echo "== 1b. the need words of the live receivers against main()'s switch (tests/cpp/need_check.cpp)"
 "$B/need_check"
+echo "== 1c. the wide-lag correlator's host translation unit (tests/cpp/san_xcorr.cpp)"
+"$B/san_xcorr"
 echo "== 2. the CPU test files against the instrumented libraries (UCHIRP_LIB / UCO_LIB), ASan runtime preloaded into python"
 LD_PRELOAD="$RT" UCHIRP_LIB="$B/libuchirp.so" UCO_LIB="$B/libuc_oracle.so" UCHIRP_ARRAY_LIB="$B/libuchirp_array.so"\
   python -m pytest "$ROOT/tests/test_array_cpu.py" "$ROOT/tests/test_group_cpu.py" "$ROOT/tests/test_oracle_golden.py" "$ROOT/tests/test_abi.py" \
