@@ -38,8 +38,9 @@
  * for FINITE inputs: the chain still multiplies the 15 neighbouring samples by 0.0f, so an infinity or a NaN within
  * -7 .. +8 samples of a sample makes that output NaN (as it does for every fractional delay).
  *
- * OUT OF SCOPE: per-microphone clock offsets (an array shares one clock); estimating the delays (that is libuchirp_align.so,
- * uchirp_align.h); adaptive weights; output formats other than float; capture into a graph.
+ * OUT OF SCOPE: per-microphone clock offsets (an array shares one clock here; libuchirp_retime.so, uchirp_retime.h, puts
+ * microphones with clocks of their own onto one first); estimating the delays (that is libuchirp_align.so, uchirp_align.h);
+ * adaptive weights; output formats other than float; capture into a graph.
  */
 #ifndef UCHIRP_ARRAY_H
 #define UCHIRP_ARRAY_H
