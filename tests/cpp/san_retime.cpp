@@ -3,9 +3,11 @@
 // fixed-point step over random values, the limits and what lies just beyond them; the table into a buffer of exactly its
 // size; every refused argument of uc_retime_rows that is decided before the object is touched; and -- where a GPU is
 // missing, as in the sanitizer's container -- the refusal of uc_retime_create.  CPU only: it never launches a kernel.
+// With UC_SAN_TEXTS set it prints the library's last error text behind every check, so that two builds can be compared.
 #include <cerrno>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <limits>
 #include <random>
@@ -19,6 +21,7 @@
       printf("san_retime: %s failed (line %d)\n", #c, __LINE__);      \
       return 1;                                                       \
     }                                                                 \
+    if (getenv("UC_SAN_TEXTS")) printf("line %d: %s\n", __LINE__, uc_retime_last_error()); \
   } while (0)
 
 // a handle that is not NULL: every refusal below is decided from the arguments alone, before the object is read
@@ -115,6 +118,7 @@ int main() {
   for (const Case& c : cases) {
     const int rc = uc_retime_rows(c.h, c.in, c.dtype, c.n_mics, c.in_first, c.n_in, c.in_stride, c.ln, c.n_lines, c.out, c.out_first,
                                   c.n_out, c.out_stride, nullptr);
+    if (getenv("UC_SAN_TEXTS")) printf("%s: %d: %s\n", c.name, rc, uc_retime_last_error());   // to compare the texts of two builds
     if (rc != -EINVAL || strlen(uc_retime_last_error()) == 0) {
       printf("san_retime: %s: rc %d (%s)\n", c.name, rc, uc_retime_last_error());
       return 1;

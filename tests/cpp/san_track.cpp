@@ -3,10 +3,12 @@
 // uc_track_finish on crafted records (empty, one slot, four slots, a tie, NOT_FINITE, slots out of range), each in a buffer
 // of exactly its size; every refused argument of uc_track_windows that is decided before the object is touched; and --
 // where a GPU is missing, as in the sanitizer's container -- the refusal of uc_track_create.  CPU only: it never launches a
-// kernel.
+// kernel.  With UC_SAN_TEXTS set it prints the library's last error text behind every check, so that two builds can be
+// compared.
 #include <cerrno>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <vector>
@@ -19,6 +21,7 @@
       printf("san_track: %s failed (line %d)\n", #c, __LINE__);      \
       return 1;                                                      \
     }                                                                \
+    if (getenv("UC_SAN_TEXTS")) printf("line %d: %s\n", __LINE__, uc_track_last_error()); \
   } while (0)
 
 // a handle that is not NULL: every refusal below is decided from the arguments alone, before the object is used
@@ -160,6 +163,7 @@ int main() {
   for (const Case& c : cases) {
     const int rc = uc_track_windows(c.h, c.in, c.dtype, c.n_mics, c.n_in, c.in_stride, c.pr, c.n_pairs, c.first, c.window_len, c.hop,
                                     c.n_windows, c.L, c.corr, c.corr_stride, c.crest, nullptr);
+    if (getenv("UC_SAN_TEXTS")) printf("%s: %d: %s\n", c.name, rc, uc_track_last_error());   // to compare the texts of two builds
     if (rc != -EINVAL || strlen(uc_track_last_error()) == 0) {
       printf("san_track: %s: rc %d (%s)\n", c.name, rc, uc_track_last_error());
       return 1;

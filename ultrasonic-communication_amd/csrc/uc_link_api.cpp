@@ -1,23 +1,19 @@
-// uc_link_api.cpp -- the C-ABI of include/uchirp_link.h on top of uc_link_kernel.hip: errors, the link object and its
-// staging buffers, argument checks, the two launches.  No CPU compute path exists here: without a usable HIP device
-// uc_link_create fails.  Every entry point leaves the calling thread's current HIP device as it found it.
+// uc_link_api.cpp -- the C-ABI of include/uchirp_link.h on top of uc_link_kernel.hip: the link object and its frame
+// format, the checks and the staging that are its own, the two launches.  The object's base, create and destroy, the
+// staging protocol, the grid and the checks of the row matrices are the shared host layer's (uc_host.hpp: header-only,
+// nothing crosses a library boundary); the frame format's checks are uc_link_host.hpp's: libuchirp_link.so stands alone.
+// No CPU compute path exists here: without a usable HIP device uc_link_create fails.  Every entry point leaves the calling
+// thread's current HIP device as it found it.
 #include "../../include/uchirp_link.h"
 #include "uc_link.hpp"
 #include "uc_link_host.hpp"
 
 using namespace uc_link_dev;
 
-struct uc_link {
-  int device = 0;
+// staging: [n_streams Stream records][n_streams * text_stride bytes]
+struct uc_link : HostBase {
   uc_link_config cfg{};
   int n_sym = 0;
-  int cus = 0;
-  unsigned grid_override = 0;      // UC_LINK_GRID under UC_TUNING=1
-  // staging: [n_streams Stream records][n_streams * text_stride bytes], pinned on the host and its twin on the device.
-  // Two such pairs, used in turn: call k stages while call k - 1's copy still waits in its stream, so that a loop of
-  // calls blocks the host only on the copy of two calls back.
-  StagingSlot slot[2];
-  unsigned next = 0;
 };
 
 extern "C" {
@@ -41,69 +37,36 @@ int uc_link_create(int device, const uc_link_config* cfg, uc_link** out) {
   else
     uc_link_default_config(&c);
   if (!config_ok(&c)) return fail(-EINVAL, "uc_link_create: not a frame format (fs_tx, t_symbol > 0, at least 2 samples per symbol)");
-  int ndev = 0;
-  hipError_t e = hipGetDeviceCount(&ndev);
-  if (e != hipSuccess || ndev <= 0) {
-    (void)hipGetLastError();
-    return fail(-ENODEV, "uc_link_create: no HIP device (%s); this library has no CPU path",
-                e != hipSuccess ? hipGetErrorString(e) : "0 devices");
-  }
-  if (device < 0 || device >= ndev) return fail(-ENODEV, "uc_link_create: device %d out of range [0,%d)", device, ndev);
   DeviceGuard guard;
-  if ((e = hipSetDevice(device)) != hipSuccess) return hip_fail(e, "uc_link_create: hipSetDevice");
-  hipDeviceProp_t prop;
-  if ((e = hipGetDeviceProperties(&prop, device)) != hipSuccess) return hip_fail(e, "uc_link_create: hipGetDeviceProperties");
-  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return fail(-ENODEV, "uc_link_create: device %d is %s; the kernels are built for gfx950 only", device, prop.gcnArchName);
-  uc_link* l = new uc_link();
-  l->device = device;
-  l->cfg = c;
-  l->n_sym = (int)(c.t_symbol * c.fs_tx);
-  l->cus = prop.multiProcessorCount;
-  // experiment switches are read only under UC_TUNING=1, so that a stray variable in a production environment changes nothing
-  const char* tuning = getenv("UC_TUNING");
-  if (tuning && !strcmp(tuning, "1")) {
-    const char* g = getenv("UC_LINK_GRID");
-    if (g && atoi(g) > 0) l->grid_override = (unsigned)atoi(g);
-  }
-  for (StagingSlot& sl : l->slot)
-    if ((e = hipEventCreateWithFlags(&sl.copied, hipEventDisableTiming)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&sl.done, hipEventDisableTiming)) != hipSuccess) {
-      uc_link_destroy(l);
-      return hip_fail(e, "uc_link_create: hipEventCreate");
-    }
-  *out = l;
+  const int rc = open("uc_link_create", "UC_LINK_GRID", device, out);
+  if (rc) return rc;
+  (*out)->cfg = c;
+  (*out)->n_sym = (int)(c.t_symbol * c.fs_tx);
   return 0;
 }
 
 void uc_link_destroy(uc_link* l) {
   if (!l) return;
   DeviceGuard guard;
-  (void)hipSetDevice(l->device);
-  for (StagingSlot& sl : l->slot) {
-    if (sl.in_flight) (void)hipEventSynchronize(sl.done);
-    if (sl.pinned) (void)hipHostFree(sl.pinned);
-    if (sl.dev) (void)hipFree(sl.dev);
-    if (sl.copied) (void)hipEventDestroy(sl.copied);
-    if (sl.done) (void)hipEventDestroy(sl.done);
-  }
+  close_base(l);
   delete l;
 }
 
 int uc_link_transmit(uc_link* l, const uint8_t* text, size_t text_stride, const uc_link_stream* params, size_t n_streams,
                      void* out_dev, int dtype, double fs_out, uint64_t first_sample, size_t n_samples, size_t stride_elems,
                      uint64_t seed, void* hip_stream) {
+  static const char WHO[] = "uc_link_transmit";
   // ---- checks: nothing is enqueued before the last of them
   if (!l) return fail(-EINVAL, "uc_link_transmit: link is NULL");
   if (!params || !out_dev) return fail(-EINVAL, "uc_link_transmit: params / out_dev is NULL");
-  if (n_streams == 0 || n_streams > 0xFFFFFFFFull) return fail(-EINVAL, "uc_link_transmit: n_streams %zu out of range", n_streams);
+  if (int rc = check_count(WHO, "n_streams", n_streams)) return rc;
   if (n_samples == 0) return fail(-EINVAL, "uc_link_transmit: n_samples is 0");
   const size_t esz = elem_size(dtype);
   if (!esz) return fail(-EINVAL, "uc_link_transmit: unknown dtype %d", dtype);
   if (!(fs_out > 0.0) || !std::isfinite(fs_out)) return fail(-EINVAL, "uc_link_transmit: fs_out must be positive");
   if (text_stride > UC_LINK_MAX_TEXT) return fail(-EINVAL, "uc_link_transmit: text_stride %zu > %d", text_stride, UC_LINK_MAX_TEXT);
-  const size_t stride = stride_elems ? stride_elems : n_samples;
-  if (stride < n_samples) return fail(-EINVAL, "uc_link_transmit: stride_elems %zu < n_samples %zu", stride_elems, n_samples);
+  const size_t stride = stride_or(stride_elems, n_samples);
+  if (int rc = check_stride(WHO, "stride_elems", stride_elems, "n_samples", n_samples)) return rc;
   if (first_sample > (1ull << 52) || n_samples > (1ull << 40)) return fail(-EINVAL, "uc_link_transmit: sample range too large");
   bool any_text = false;
   for (size_t s = 0; s < n_streams; ++s) {
@@ -117,19 +80,17 @@ int uc_link_transmit(uc_link* l, const uint8_t* text, size_t text_stride, const 
   if (any_text && !text) return fail(-EINVAL, "uc_link_transmit: text is NULL");
   DeviceGuard guard;
   hipError_t e = hipSetDevice(l->device);
-  if (e != hipSuccess) return hip_fail(e, "uc_link_transmit: hipSetDevice");
+  if (e != hipSuccess) return hip_fail(e, WHO, "hipSetDevice");
   if (!is_device_ptr(out_dev)) return fail(-EINVAL, "uc_link_transmit: out_dev is not device memory");
   const uint64_t first_quad = first_sample / 4, end_quad = (first_sample + n_samples + 3) / 4;
   const uint64_t tiles_per_stream = (end_quad - first_quad + TILE_QUADS - 1) / TILE_QUADS;
   const size_t rec_bytes = n_streams * sizeof(Stream);
   const size_t bytes = rec_bytes + n_streams * text_stride;
-  StagingSlot& sl = l->slot[l->next];
-  int rc = reserve(&sl, bytes, "uc_link_transmit");
-  if (rc) return rc;
+  StagingSlot* sl;
+  if (int rc = stage_begin(l, bytes, WHO, &sl)) return rc;
 
-  // ---- stage (this slot's pinned buffer is free once the copy of two calls back has run)
-  if (sl.in_flight) (void)hipEventSynchronize(sl.copied);
-  Stream* rec = (Stream*)sl.pinned;
+  // ---- stage
+  Stream* rec = (Stream*)sl->pinned;
   for (size_t s = 0; s < n_streams; ++s) {
     const uc_link_stream& q = params[s];
     rec[s].rate = (1.0 / fs_out) * (1.0 + (double)q.ppm * 1e-6);
@@ -141,9 +102,9 @@ int uc_link_transmit(uc_link* l, const uint8_t* text, size_t text_stride, const 
   }
   if (text_stride) {
     if (text)
-      memcpy((char*)sl.pinned + rec_bytes, text, n_streams * text_stride);
+      memcpy((char*)sl->pinned + rec_bytes, text, n_streams * text_stride);
     else
-      memset((char*)sl.pinned + rec_bytes, 0, n_streams * text_stride);
+      memset((char*)sl->pinned + rec_bytes, 0, n_streams * text_stride);
   }
   Params p;
   memset(&p, 0, sizeof(p));
@@ -170,16 +131,9 @@ int uc_link_transmit(uc_link* l, const uint8_t* text, size_t text_stride, const 
 
   // ---- enqueue
   hipStream_t hs = (hipStream_t)hip_stream;
-  if (sl.in_flight && (e = hipStreamWaitEvent(hs, sl.done, 0)) != hipSuccess) return hip_fail(e, "uc_link_transmit: hipStreamWaitEvent");
-  if ((e = hipMemcpyAsync(sl.dev, sl.pinned, bytes, hipMemcpyHostToDevice, hs)) != hipSuccess)
-    return hip_fail(e, "uc_link_transmit: hipMemcpyAsync");
-  (void)hipEventRecord(sl.copied, hs);
-  e = (hipError_t)launch_transmit(dtype, (unsigned)grid, hs, p, (const Stream*)sl.dev, (const uint8_t*)sl.dev + rec_bytes, out_dev);
-  (void)hipEventRecord(sl.done, hs);
-  sl.in_flight = true;
-  l->next ^= 1u;
-  if (e != hipSuccess) return hip_fail(e, "uc_link_transmit: launch");
-  return 0;
+  if (int rc = stage_copy(sl, bytes, hs, WHO)) return rc;
+  e = (hipError_t)launch_transmit(dtype, (unsigned)grid, hs, p, (const Stream*)sl->dev, (const uint8_t*)sl->dev + rec_bytes, out_dev);
+  return stage_end(l, sl, hs, e, WHO);
 }
 
 int uc_link_noise_words(uc_link* l, uint64_t seed, uint64_t stream, uint64_t first_counter, size_t n_counters, uint32_t* out_dev,
@@ -189,13 +143,13 @@ int uc_link_noise_words(uc_link* l, uint64_t seed, uint64_t stream, uint64_t fir
   if (n_counters == 0 || n_counters > (1ull << 40)) return fail(-EINVAL, "uc_link_noise_words: n_counters %zu out of range", n_counters);
   DeviceGuard guard;
   hipError_t e = hipSetDevice(l->device);
-  if (e != hipSuccess) return hip_fail(e, "uc_link_noise_words: hipSetDevice");
+  if (e != hipSuccess) return hip_fail(e, "uc_link_noise_words", "hipSetDevice");
   if (!is_device_ptr(out_dev)) return fail(-EINVAL, "uc_link_noise_words: out_dev is not device memory");
   uint64_t grid = (n_counters + THREADS - 1) / THREADS;
   const uint64_t cap = (uint64_t)l->cus * 8;
   if (grid > cap) grid = cap;
   e = (hipError_t)launch_words((unsigned)grid, hip_stream, seed, stream, first_counter, n_counters, out_dev);
-  if (e != hipSuccess) return hip_fail(e, "uc_link_noise_words: launch");
+  if (e != hipSuccess) return hip_fail(e, "uc_link_noise_words", "launch");
   return 0;
 }
 

@@ -1,8 +1,9 @@
-// uc_retime_api.cpp -- the C-ABI of include/uchirp_retime.h on top of uc_retime_kernel.hip: errors, the object, its table
-// and its staging buffers, the fixed-point step, argument checks, the launch.  Built like uc_array_api.cpp, with the same
-// host-side helpers (uc_host.hpp: header-only, nothing crosses a library boundary): libuchirp_retime.so stands alone.  No
-// CPU compute path exists here: without a usable HIP device uc_retime_create fails.  Every entry point leaves the calling
-// thread's current HIP device as it found it.
+// uc_retime_api.cpp -- the C-ABI of include/uchirp_retime.h on top of uc_retime_kernel.hip: the object and its table, the
+// fixed-point step, the checks and the staging that are its own, the launch.  The object's base, create and destroy, the
+// staging protocol, the grid and the checks of the row matrices are the shared host layer's (uc_host.hpp: header-only,
+// nothing crosses a library boundary): libuchirp_retime.so stands alone.  No CPU compute path exists here: without a
+// usable HIP device uc_retime_create fails.  Every entry point leaves the calling thread's current HIP device as it found
+// it.
 #include "../../include/uchirp_retime.h"
 #include "uc_host.hpp"
 #include "uc_retime.hpp"
@@ -13,16 +14,9 @@ static_assert(sizeof(uc_retime_line) == 24 && sizeof(Line) == 24, "layouts of uc
 static_assert(UC_RETIME_COEFS == COEFS && UC_RETIME_TABLE_ROWS == TABLE_ROWS, "the table's shape");
 static_assert(UC_RETIME_DTYPE_I32 == DT_I32 && UC_RETIME_DTYPE_F32 == DT_F32, "dtype values");
 
-struct uc_retime {
-  int device = 0;
-  int cus = 0;
-  unsigned grid_override = 0;      // UC_RETIME_GRID under UC_TUNING=1
-  int resident[2] = {0, 0};        // by dtype: workgroups one CU holds at once (asked once per format)
+// staging: [n_lines Line records]
+struct uc_retime : HostBase {
   float* table = nullptr;          // T[257][16] on the device, written once by uc_retime_create
-  // staging: [n_lines Line records], pinned on the host and its twin on the device.  Two such pairs, used in turn: call k
-  // stages while call k - 1's copy still waits in its stream.
-  StagingSlot slot[2];
-  unsigned next = 0;
 };
 
 namespace {
@@ -95,60 +89,27 @@ int uc_retime_table(float table[UC_RETIME_TABLE_ROWS * UC_RETIME_COEFS]) {
 }
 
 int uc_retime_create(int device, uc_retime** out) {
-  if (!out) return fail(-EINVAL, "uc_retime_create: out is NULL");
-  *out = nullptr;
-  int ndev = 0;
-  hipError_t e = hipGetDeviceCount(&ndev);
-  if (e != hipSuccess || ndev <= 0) {
-    (void)hipGetLastError();
-    return fail(-ENODEV, "uc_retime_create: no HIP device (%s); this library has no CPU path",
-                e != hipSuccess ? hipGetErrorString(e) : "0 devices");
-  }
-  if (device < 0 || device >= ndev) return fail(-ENODEV, "uc_retime_create: device %d out of range [0,%d)", device, ndev);
   DeviceGuard guard;
-  if ((e = hipSetDevice(device)) != hipSuccess) return hip_fail(e, "uc_retime_create: hipSetDevice");
-  hipDeviceProp_t prop;
-  if ((e = hipGetDeviceProperties(&prop, device)) != hipSuccess) return hip_fail(e, "uc_retime_create: hipGetDeviceProperties");
-  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return fail(-ENODEV, "uc_retime_create: device %d is %s; the kernels are built for gfx950 only", device, prop.gcnArchName);
-  uc_retime* l = new uc_retime();
-  l->device = device;
-  l->cus = prop.multiProcessorCount;
-  // experiment switches are read only under UC_TUNING=1, so that a stray variable in a production environment changes nothing
-  const char* tuning = getenv("UC_TUNING");
-  if (tuning && !strcmp(tuning, "1")) {
-    const char* g = getenv("UC_RETIME_GRID");
-    if (g && atoi(g) > 0) l->grid_override = (unsigned)atoi(g);
-  }
-  for (StagingSlot& sl : l->slot)
-    if ((e = hipEventCreateWithFlags(&sl.copied, hipEventDisableTiming)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&sl.done, hipEventDisableTiming)) != hipSuccess) {
-      uc_retime_destroy(l);
-      return hip_fail(e, "uc_retime_create: hipEventCreate");
-    }
+  int rc = open("uc_retime_create", "UC_RETIME_GRID", device, out);
+  if (rc) return rc;
   // the table: computed once, copied with a synchronous copy (pageable memory: done when the call returns)
+  uc_retime* l = *out;
   float host_table[TABLE_ROWS * COEFS];
   fill_table(host_table);
+  hipError_t e;
   if ((e = hipMalloc((void**)&l->table, sizeof(host_table))) != hipSuccess ||
       (e = hipMemcpy(l->table, host_table, sizeof(host_table), hipMemcpyHostToDevice)) != hipSuccess) {
     uc_retime_destroy(l);
-    return hip_fail(e, "uc_retime_create: the table");
+    *out = nullptr;
+    return hip_fail(e, "uc_retime_create", "the table");
   }
-  *out = l;
   return 0;
 }
 
 void uc_retime_destroy(uc_retime* l) {
   if (!l) return;
   DeviceGuard guard;
-  (void)hipSetDevice(l->device);
-  for (StagingSlot& sl : l->slot) {
-    if (sl.in_flight) (void)hipEventSynchronize(sl.done);
-    if (sl.pinned) (void)hipHostFree(sl.pinned);
-    if (sl.dev) (void)hipFree(sl.dev);
-    if (sl.copied) (void)hipEventDestroy(sl.copied);
-    if (sl.done) (void)hipEventDestroy(sl.done);
-  }
+  close_base(l);
   if (l->table) (void)hipFree(l->table);
   delete l;
 }
@@ -156,24 +117,23 @@ void uc_retime_destroy(uc_retime* l) {
 int uc_retime_rows(uc_retime* l, const void* in_dev, int in_dtype, size_t n_mics, uint64_t in_first, size_t n_in, size_t in_stride,
                    const uc_retime_line* lines, size_t n_lines, float* out_dev, uint64_t out_first, size_t n_out, size_t out_stride,
                    void* hip_stream) {
+  static const char WHO[] = "uc_retime_rows";
   // ---- checks: nothing is enqueued before the last of them
   if (!l) return fail(-EINVAL, "uc_retime_rows: retime is NULL");
   if (!in_dev || !out_dev) return fail(-EINVAL, "uc_retime_rows: in_dev or out_dev is NULL");
   if (!lines) return fail(-EINVAL, "uc_retime_rows: lines is NULL");
-  if (in_dtype != UC_RETIME_DTYPE_I32 && in_dtype != UC_RETIME_DTYPE_F32) return fail(-EINVAL, "uc_retime_rows: unknown dtype %d", in_dtype);
-  if (n_mics == 0 || n_mics > 0xFFFFFFFFull) return fail(-EINVAL, "uc_retime_rows: n_mics %zu out of range", n_mics);
-  if (n_lines == 0 || n_lines > 0xFFFFFFFFull) return fail(-EINVAL, "uc_retime_rows: n_lines %zu out of range", n_lines);
+  if (int rc = check_dtype(WHO, in_dtype)) return rc;
+  if (int rc = check_count(WHO, "n_mics", n_mics)) return rc;
+  if (int rc = check_count(WHO, "n_lines", n_lines)) return rc;
   if (n_in == 0 || n_out == 0) return fail(-EINVAL, "uc_retime_rows: n_in or n_out is 0");
   if (in_first > (1ull << 52) || n_in > (1ull << 40)) return fail(-EINVAL, "uc_retime_rows: sample range too large");
   if (out_first > SAMPLE_END_MAX || n_out > SAMPLE_END_MAX || out_first + n_out > SAMPLE_END_MAX)
     return fail(-EINVAL, "uc_retime_rows: out_first + n_out > 2^38");
-  const size_t istride = in_stride ? in_stride : n_in, ostride = out_stride ? out_stride : n_out;
-  if (istride < n_in) return fail(-EINVAL, "uc_retime_rows: in_stride %zu < n_in %zu", in_stride, n_in);
-  if (ostride < n_out) return fail(-EINVAL, "uc_retime_rows: out_stride %zu < n_out %zu", out_stride, n_out);
-  if (istride > (1ull << 40) || ostride > (1ull << 40)) return fail(-EINVAL, "uc_retime_rows: stride too large");
-  // counts are below 2^32 and strides at most 2^40, so the products below cannot wrap; a buffer of 2^60 bytes is no buffer
-  if ((uint64_t)n_mics * istride > (1ull << 58) || (uint64_t)n_lines * ostride > (1ull << 58))
-    return fail(-EINVAL, "uc_retime_rows: n_mics * in_stride or n_lines * out_stride too large");
+  const size_t istride = stride_or(in_stride, n_in), ostride = stride_or(out_stride, n_out);
+  if (int rc = check_stride(WHO, "in_stride", in_stride, "n_in", n_in)) return rc;
+  if (int rc = check_stride(WHO, "out_stride", out_stride, "n_out", n_out)) return rc;
+  if (int rc = check_strides_max(WHO, istride, ostride)) return rc;
+  if (int rc = check_extent(WHO, n_mics, istride, n_lines, ostride, 1ull << 58, "n_lines * out_stride")) return rc;
   for (size_t k = 0; k < n_lines; ++k) {
     const uc_retime_line& q = lines[k];
     if (q.mic >= n_mics) return fail(-EINVAL, "uc_retime_rows: line %zu: mic %u >= n_mics %zu", k, q.mic, n_mics);
@@ -181,22 +141,19 @@ int uc_retime_rows(uc_retime* l, const void* in_dev, int in_dtype, size_t n_mics
     if (!line_ok(q.delay_samples, q.slope))
       return fail(-EINVAL, "uc_retime_rows: line %zu: delay_samples and slope must be finite, |delay_samples| <= 2^30, |slope| <= 2^-9", k);
   }
-  const uintptr_t ia = (uintptr_t)in_dev, ib = ia + ((n_mics - 1) * istride + n_in) * 4;
-  const uintptr_t oa = (uintptr_t)out_dev, ob = oa + ((n_lines - 1) * ostride + n_out) * 4;
-  if (oa < ib && ia < ob) return fail(-EINVAL, "uc_retime_rows: out_dev overlaps in_dev");
+  if (int rc = check_disjoint(WHO, "out_dev", out_dev, span_bytes(n_lines, ostride, n_out, 4), "in_dev", in_dev, span_bytes(n_mics, istride, n_in, 4)))
+    return rc;
   DeviceGuard guard;
   hipError_t e = hipSetDevice(l->device);
-  if (e != hipSuccess) return hip_fail(e, "uc_retime_rows: hipSetDevice");
-  if (device_of(in_dev) != l->device) return fail(-EINVAL, "uc_retime_rows: in_dev is not device memory of device %d", l->device);
-  if (device_of(out_dev) != l->device) return fail(-EINVAL, "uc_retime_rows: out_dev is not device memory of device %d", l->device);
+  if (e != hipSuccess) return hip_fail(e, WHO, "hipSetDevice");
+  if (int rc = check_on_device(WHO, "in_dev", in_dev, l->device)) return rc;
+  if (int rc = check_on_device(WHO, "out_dev", out_dev, l->device)) return rc;
   const size_t bytes = n_lines * sizeof(Line);
-  StagingSlot& sl = l->slot[l->next];
-  int rc = reserve(&sl, bytes, "uc_retime_rows");
-  if (rc) return rc;
+  StagingSlot* sl;
+  if (int rc = stage_begin(l, bytes, WHO, &sl)) return rc;
 
-  // ---- stage (this slot's pinned buffer is free once the copy of two calls back has run)
-  if (sl.in_flight) (void)hipEventSynchronize(sl.copied);
-  Line* rec = (Line*)sl.pinned;
+  // ---- stage
+  Line* rec = (Line*)sl->pinned;
   for (size_t k = 0; k < n_lines; ++k) {
     rec[k].lead_fx = (int64_t)std::llrint(lines[k].delay_samples * TWO32);
     rec[k].drift_fx = (int64_t)std::llrint(lines[k].slope * TWO32);
@@ -215,29 +172,13 @@ int uc_retime_rows(uc_retime* l, const void* in_dev, int in_dtype, size_t n_mics
   const uint64_t tiles_per_row = (n_out + TILE_SAMPLES - 1) / TILE_SAMPLES;
   p.tiles_per_row = (uint32_t)tiles_per_row;
   p.n_lines = (uint32_t)n_lines;
-  const uint64_t n_tiles = (uint64_t)n_lines * tiles_per_row;
-  // a persistent grid of exactly the workgroups the chip holds at once (the tiles are dealt statically); the runtime's
-  // occupancy figure is asked, not assumed
-  if (!l->resident[in_dtype]) {
-    const int r = resident_blocks_per_cu(in_dtype);
-    l->resident[in_dtype] = r > 0 ? r : 4;
-  }
-  uint64_t grid = (uint64_t)l->cus * (uint64_t)l->resident[in_dtype];
-  if (l->grid_override) grid = l->grid_override;
-  if (grid > n_tiles) grid = n_tiles;
+  const uint64_t grid = persistent_grid(l, in_dtype, resident_blocks_per_cu, 4, (uint64_t)n_lines * tiles_per_row);
 
   // ---- enqueue
   hipStream_t hs = (hipStream_t)hip_stream;
-  if (sl.in_flight && (e = hipStreamWaitEvent(hs, sl.done, 0)) != hipSuccess) return hip_fail(e, "uc_retime_rows: hipStreamWaitEvent");
-  if ((e = hipMemcpyAsync(sl.dev, sl.pinned, bytes, hipMemcpyHostToDevice, hs)) != hipSuccess)
-    return hip_fail(e, "uc_retime_rows: hipMemcpyAsync");
-  (void)hipEventRecord(sl.copied, hs);
-  e = (hipError_t)launch_rows(in_dtype, (unsigned)grid, hs, p, (const Line*)sl.dev);
-  (void)hipEventRecord(sl.done, hs);
-  sl.in_flight = true;
-  l->next ^= 1u;
-  if (e != hipSuccess) return hip_fail(e, "uc_retime_rows: launch");
-  return 0;
+  if (int rc = stage_copy(sl, bytes, hs, WHO)) return rc;
+  e = (hipError_t)launch_rows(in_dtype, (unsigned)grid, hs, p, (const Line*)sl->dev);
+  return stage_end(l, sl, hs, e, WHO);
 }
 
 }  // extern "C"

@@ -1,5 +1,7 @@
-// uc_scene_api.cpp -- the C-ABI of include/uchirp_scene.h on top of uc_scene_kernel.hip: errors, the scene object and
-// its staging buffers, argument checks, the launch.  Built like uc_link_api.cpp and sharing nothing with it at link time:
+// uc_scene_api.cpp -- the C-ABI of include/uchirp_scene.h on top of uc_scene_kernel.hip: the scene object and its frame
+// format, the checks and the staging that are its own, the launch.  The object's base, create and destroy, the staging
+// protocol, the grid and the checks of the row matrices are the shared host layer's (uc_host.hpp: header-only, nothing
+// crosses a library boundary); the frame format's checks are uc_link_host.hpp's, shared with uc_link_api.cpp at no symbol:
 // libuchirp_scene.so stands alone.  No CPU compute path exists here: without a usable HIP device uc_scene_create fails.
 // Every entry point leaves the calling thread's current HIP device as it found it.
 #include "../../include/uchirp_scene.h"
@@ -8,18 +10,10 @@
 
 using namespace uc_scene_dev;
 
-struct uc_scene {
-  int device = 0;
+// staging: [n_paths Path records][n_mics Mic records][n_tx * text_stride bytes]
+struct uc_scene : HostBase {
   uc_link_config cfg{};
   int n_sym = 0;
-  int cus = 0;
-  unsigned grid_override = 0;      // UC_SCENE_GRID under UC_TUNING=1
-  int resident[4] = {0, 0, 0, 0};  // by dtype: workgroups one CU holds at once (asked once per format)
-  // staging: [n_paths Path records][n_mics Mic records][n_tx * text_stride bytes], pinned on the host and its twin on the device.
-  // Two such pairs, used in turn: call k stages while call k - 1's copy still waits in its stream, so that a loop of
-  // calls blocks the host only on the copy of two calls back.
-  StagingSlot slot[2];
-  unsigned next = 0;
 };
 
 extern "C" {
@@ -43,62 +37,29 @@ int uc_scene_create(int device, const uc_link_config* cfg, uc_scene** out) {
   else
     uc_scene_default_config(&c);
   if (!config_ok(&c)) return fail(-EINVAL, "uc_scene_create: not a frame format (fs_tx, t_symbol > 0, at least 2 samples per symbol)");
-  int ndev = 0;
-  hipError_t e = hipGetDeviceCount(&ndev);
-  if (e != hipSuccess || ndev <= 0) {
-    (void)hipGetLastError();
-    return fail(-ENODEV, "uc_scene_create: no HIP device (%s); this library has no CPU path",
-                e != hipSuccess ? hipGetErrorString(e) : "0 devices");
-  }
-  if (device < 0 || device >= ndev) return fail(-ENODEV, "uc_scene_create: device %d out of range [0,%d)", device, ndev);
   DeviceGuard guard;
-  if ((e = hipSetDevice(device)) != hipSuccess) return hip_fail(e, "uc_scene_create: hipSetDevice");
-  hipDeviceProp_t prop;
-  if ((e = hipGetDeviceProperties(&prop, device)) != hipSuccess) return hip_fail(e, "uc_scene_create: hipGetDeviceProperties");
-  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return fail(-ENODEV, "uc_scene_create: device %d is %s; the kernels are built for gfx950 only", device, prop.gcnArchName);
-  uc_scene* l = new uc_scene();
-  l->device = device;
-  l->cfg = c;
-  l->n_sym = (int)(c.t_symbol * c.fs_tx);
-  l->cus = prop.multiProcessorCount;
-  // experiment switches are read only under UC_TUNING=1, so that a stray variable in a production environment changes nothing
-  const char* tuning = getenv("UC_TUNING");
-  if (tuning && !strcmp(tuning, "1")) {
-    const char* g = getenv("UC_SCENE_GRID");
-    if (g && atoi(g) > 0) l->grid_override = (unsigned)atoi(g);
-  }
-  for (StagingSlot& sl : l->slot)
-    if ((e = hipEventCreateWithFlags(&sl.copied, hipEventDisableTiming)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&sl.done, hipEventDisableTiming)) != hipSuccess) {
-      uc_scene_destroy(l);
-      return hip_fail(e, "uc_scene_create: hipEventCreate");
-    }
-  *out = l;
+  const int rc = open("uc_scene_create", "UC_SCENE_GRID", device, out);
+  if (rc) return rc;
+  (*out)->cfg = c;
+  (*out)->n_sym = (int)(c.t_symbol * c.fs_tx);
   return 0;
 }
 
 void uc_scene_destroy(uc_scene* l) {
   if (!l) return;
   DeviceGuard guard;
-  (void)hipSetDevice(l->device);
-  for (StagingSlot& sl : l->slot) {
-    if (sl.in_flight) (void)hipEventSynchronize(sl.done);
-    if (sl.pinned) (void)hipHostFree(sl.pinned);
-    if (sl.dev) (void)hipFree(sl.dev);
-    if (sl.copied) (void)hipEventDestroy(sl.copied);
-    if (sl.done) (void)hipEventDestroy(sl.done);
-  }
+  close_base(l);
   delete l;
 }
 
 int uc_scene_render(uc_scene* l, const uint8_t* text, size_t text_stride, const uint32_t* text_len, size_t n_tx,
                     const uc_scene_path* paths, size_t n_paths, const uc_scene_mic* mics, size_t n_mics, void* out_dev, int dtype,
                     double fs_out, uint64_t first_sample, size_t n_samples, size_t stride_elems, uint64_t seed, void* hip_stream) {
+  static const char WHO[] = "uc_scene_render";
   // ---- checks: nothing is enqueued before the last of them
   if (!l) return fail(-EINVAL, "uc_scene_render: scene is NULL");
   if (!out_dev) return fail(-EINVAL, "uc_scene_render: out_dev is NULL");
-  if (n_mics == 0 || n_mics > 0xFFFFFFFFull) return fail(-EINVAL, "uc_scene_render: n_mics %zu out of range", n_mics);
+  if (int rc = check_count(WHO, "n_mics", n_mics)) return rc;
   if (n_paths > 0xFFFFFFFFull || n_tx > 0xFFFFFFFFull) return fail(-EINVAL, "uc_scene_render: n_paths / n_tx out of range");
   if (!mics) return fail(-EINVAL, "uc_scene_render: mics is NULL");
   if (n_paths && !paths) return fail(-EINVAL, "uc_scene_render: paths is NULL, n_paths %zu", n_paths);
@@ -108,8 +69,8 @@ int uc_scene_render(uc_scene* l, const uint8_t* text, size_t text_stride, const 
   if (!esz) return fail(-EINVAL, "uc_scene_render: unknown dtype %d", dtype);
   if (!(fs_out > 0.0) || !std::isfinite(fs_out)) return fail(-EINVAL, "uc_scene_render: fs_out must be positive");
   if (text_stride > UC_LINK_MAX_TEXT) return fail(-EINVAL, "uc_scene_render: text_stride %zu > %d", text_stride, UC_LINK_MAX_TEXT);
-  const size_t stride = stride_elems ? stride_elems : n_samples;
-  if (stride < n_samples) return fail(-EINVAL, "uc_scene_render: stride_elems %zu < n_samples %zu", stride_elems, n_samples);
+  const size_t stride = stride_or(stride_elems, n_samples);
+  if (int rc = check_stride(WHO, "stride_elems", stride_elems, "n_samples", n_samples)) return rc;
   if (first_sample > (1ull << 52) || n_samples > (1ull << 40)) return fail(-EINVAL, "uc_scene_render: sample range too large");
   bool any_text = false;
   for (size_t t = 0; t < n_tx; ++t) {
@@ -135,20 +96,18 @@ int uc_scene_render(uc_scene* l, const uint8_t* text, size_t text_stride, const 
   }
   DeviceGuard guard;
   hipError_t e = hipSetDevice(l->device);
-  if (e != hipSuccess) return hip_fail(e, "uc_scene_render: hipSetDevice");
+  if (e != hipSuccess) return hip_fail(e, WHO, "hipSetDevice");
   if (!is_device_ptr(out_dev)) return fail(-EINVAL, "uc_scene_render: out_dev is not device memory");
   const uint64_t first_quad = first_sample / 4, end_quad = (first_sample + n_samples + 3) / 4;
   const uint64_t tiles_per_mic = (end_quad - first_quad + TILE_QUADS - 1) / TILE_QUADS;
   const size_t path_bytes = n_paths * sizeof(Path), mic_bytes = n_mics * sizeof(Mic);
   const size_t bytes = path_bytes + mic_bytes + n_tx * text_stride;
-  StagingSlot& sl = l->slot[l->next];
-  int rc = reserve(&sl, bytes, "uc_scene_render");
-  if (rc) return rc;
+  StagingSlot* sl;
+  if (int rc = stage_begin(l, bytes, WHO, &sl)) return rc;
 
-  // ---- stage (this slot's pinned buffer is free once the copy of two calls back has run)
-  if (sl.in_flight) (void)hipEventSynchronize(sl.copied);
+  // ---- stage
   const uc_link_config& c = l->cfg;
-  Path* prec = (Path*)sl.pinned;
+  Path* prec = (Path*)sl->pinned;
   for (size_t k = 0; k < n_paths; ++k) {
     const uc_scene_path& q = paths[k];
     prec[k].rate = (1.0 / fs_out) * (1.0 + (double)q.ppm * 1e-6);
@@ -158,7 +117,7 @@ int uc_scene_render(uc_scene* l, const uint8_t* text, size_t text_stride, const 
     prec[k].tx = q.tx;
     prec[k].pad = 0;
   }
-  Mic* mrec = (Mic*)((char*)sl.pinned + path_bytes);
+  Mic* mrec = (Mic*)((char*)sl->pinned + path_bytes);
   for (size_t m = 0; m < n_mics; ++m) {
     mrec[m].first_path = mics[m].first_path;
     mrec[m].n_paths = mics[m].n_paths;
@@ -167,9 +126,9 @@ int uc_scene_render(uc_scene* l, const uint8_t* text, size_t text_stride, const 
   }
   if (n_tx * text_stride) {
     if (text)
-      memcpy((char*)sl.pinned + path_bytes + mic_bytes, text, n_tx * text_stride);
+      memcpy((char*)sl->pinned + path_bytes + mic_bytes, text, n_tx * text_stride);
     else
-      memset((char*)sl.pinned + path_bytes + mic_bytes, 0, n_tx * text_stride);
+      memset((char*)sl->pinned + path_bytes + mic_bytes, 0, n_tx * text_stride);
   }
   Params p;
   memset(&p, 0, sizeof(p));
@@ -188,32 +147,16 @@ int uc_scene_render(uc_scene* l, const uint8_t* text, size_t text_stride, const 
   p.n_preamble = c.n_preamble;
   p.text_stride = (uint32_t)text_stride;
   p.n_streams = (uint32_t)n_mics;
-  const uint64_t n_tiles = (uint64_t)n_mics * tiles_per_mic;
-  // a persistent grid of exactly the workgroups the chip holds at once: the tiles are dealt statically, so a workgroup
-  // that had to wait for a slot would run its whole share alone after the others.  The scene kernels' scalar registers
-  // leave 7 workgroups of 4 waves per CU where the link kernel has 8; the runtime's figure is asked, not assumed.
-  if (!l->resident[dtype]) {
-    const int r = resident_blocks_per_cu(dtype);
-    l->resident[dtype] = r > 0 ? r : 7;
-  }
-  uint64_t grid = (uint64_t)l->cus * (uint64_t)l->resident[dtype];
-  if (l->grid_override) grid = l->grid_override;
-  if (grid > n_tiles) grid = n_tiles;
+  // the scene kernels' scalar registers leave 7 workgroups of 4 waves per CU where the link kernel has 8
+  const uint64_t grid = persistent_grid(l, dtype, resident_blocks_per_cu, 7, (uint64_t)n_mics * tiles_per_mic);
 
   // ---- enqueue
   hipStream_t hs = (hipStream_t)hip_stream;
-  if (sl.in_flight && (e = hipStreamWaitEvent(hs, sl.done, 0)) != hipSuccess) return hip_fail(e, "uc_scene_render: hipStreamWaitEvent");
-  if ((e = hipMemcpyAsync(sl.dev, sl.pinned, bytes, hipMemcpyHostToDevice, hs)) != hipSuccess)
-    return hip_fail(e, "uc_scene_render: hipMemcpyAsync");
-  (void)hipEventRecord(sl.copied, hs);
-  const char* d = (const char*)sl.dev;
+  if (int rc = stage_copy(sl, bytes, hs, WHO)) return rc;
+  const char* d = (const char*)sl->dev;
   e = (hipError_t)launch_render(dtype, (unsigned)grid, hs, p, (const Mic*)(d + path_bytes), (const Path*)d,
                                 (const uint8_t*)(d + path_bytes + mic_bytes), out_dev);
-  (void)hipEventRecord(sl.done, hs);
-  sl.in_flight = true;
-  l->next ^= 1u;
-  if (e != hipSuccess) return hip_fail(e, "uc_scene_render: launch");
-  return 0;
+  return stage_end(l, sl, hs, e, WHO);
 }
 
 }  // extern "C"

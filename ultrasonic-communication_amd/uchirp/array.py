@@ -12,14 +12,10 @@ where the microphone hears the wanted sound `delay_samples` later than the beam'
 delay-and-sum beam from the microphones' leads.  `model` is the same definition in numpy / float64.
 """
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-_PKG = os.path.dirname(os.path.abspath(__file__))
-_ROOT = os.path.dirname(_PKG)  # ultrasonic-communication_amd/
-LIB_PATH = os.environ.get("UCHIRP_ARRAY_LIB") or os.path.join(_ROOT, "libuchirp_array.so")  # UCHIRP_ARRAY_LIB: diagnostic builds
+from ._binding import Binding
 
 ABI_VERSION = 1
 DTYPE_I32, DTYPE_F32 = 0, 1
@@ -48,51 +44,15 @@ class ArrayError(RuntimeError):
     pass
 
 
-def build(force=False):
-    """Compile libuchirp_array.so for gfx950 with hipcc (in-tree)."""
-    if os.environ.get("UCHIRP_ARRAY_LIB"):    # a diagnostic build named by the caller: it is what it is
-        return LIB_PATH
-    if force or not os.path.exists(LIB_PATH):
-        subprocess.check_call(["make", "-C", _ROOT] + (["-B"] if force else []) + ["libuchirp_array.so"])
-    else:
-        subprocess.check_call(["make", "-C", _ROOT, "libuchirp_array.so"], stdout=subprocess.DEVNULL)
-    return LIB_PATH
-
-
-_lib = None
-
-
-def lib():
-    """Load libuchirp_array.so; raises ArrayError if it is absent (no fallback)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    # one process, ONE HIP runtime: torch's bundled libamdhip64 first (see uchirp.lib())
-    try:
-        import torch  # noqa: F401
-    except ImportError:
-        pass
-    if not os.path.exists(LIB_PATH):
-        raise ArrayError("libuchirp_array.so not built: run `make -C %s libuchirp_array.so` (hipcc, gfx950); "
-                         "there is no CPU fallback" % _ROOT)
-    L = C.CDLL(LIB_PATH)
-    L.uc_array_abi_version.restype = C.c_int
-    L.uc_array_last_error.restype = C.c_char_p
+def _declare(L):
     L.uc_array_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-    L.uc_array_destroy.argtypes = [C.c_void_p]
-    L.uc_array_destroy.restype = None
     L.uc_array_tap_coefficients.argtypes = [C.c_double, C.c_float, C.POINTER(C.c_int64), C.POINTER(C.c_float)]
     L.uc_array_combine.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_uint64, C.c_size_t, C.c_size_t, C.c_void_p,
                                    C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint64, C.c_size_t, C.c_size_t, C.c_void_p]
-    _lib = L
-    return L
 
 
-def _check(rc, what):
-    if rc < 0:
-        msg = lib().uc_array_last_error()
-        raise ArrayError("%s failed (rc=%d): %s" % (what, rc, msg.decode() if msg else ""))
-    return rc
+_so = Binding("array", ArrayError, _declare, env="UCHIRP_ARRAY_LIB")  # UCHIRP_ARRAY_LIB: diagnostic builds
+LIB_PATH, build, lib, _check = _so.path, _so.build, _so.lib, _so.check
 
 
 def coefficients(delay, weight=1.0):

@@ -9,16 +9,11 @@ fractional lead, Philox4x32-10 and Box-Muller.  It is what the tests hold the ke
 a GPU can call; it is slow (one stream at a time) and never used by `Link`.
 """
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 from . import tx
-
-_PKG = os.path.dirname(os.path.abspath(__file__))
-_ROOT = os.path.dirname(_PKG)  # ultrasonic-communication_amd/
-LIB_PATH = os.path.join(_ROOT, "libuchirp_link.so")
+from ._binding import Binding
 
 ABI_VERSION = 1
 DTYPE_I32, DTYPE_F32, DTYPE_I16 = 0, 1, 3
@@ -46,50 +41,16 @@ class LinkError(RuntimeError):
     pass
 
 
-def build(force=False):
-    """Compile libuchirp_link.so for gfx950 with hipcc (in-tree)."""
-    if force or not os.path.exists(LIB_PATH):
-        subprocess.check_call(["make", "-C", _ROOT] + (["-B"] if force else []) + ["libuchirp_link.so"])
-    else:
-        subprocess.check_call(["make", "-C", _ROOT, "libuchirp_link.so"], stdout=subprocess.DEVNULL)
-    return LIB_PATH
-
-
-_lib = None
-
-
-def lib():
-    """Load libuchirp_link.so; raises LinkError if it is absent (no fallback)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    # one process, ONE HIP runtime: torch's bundled libamdhip64 first (see uchirp.lib())
-    try:
-        import torch  # noqa: F401
-    except ImportError:
-        pass
-    if not os.path.exists(LIB_PATH):
-        raise LinkError("libuchirp_link.so not built: run `make -C %s libuchirp_link.so` (hipcc, gfx950); "
-                        "there is no CPU fallback" % _ROOT)
-    L = C.CDLL(LIB_PATH)
-    L.uc_link_abi_version.restype = C.c_int
-    L.uc_link_last_error.restype = C.c_char_p
+def _declare(L):
     L.uc_link_default_config.argtypes = [C.POINTER(LinkConfig)]
     L.uc_link_create.argtypes = [C.c_int, C.POINTER(LinkConfig), C.POINTER(C.c_void_p)]
-    L.uc_link_destroy.argtypes = [C.c_void_p]
-    L.uc_link_destroy.restype = None
     L.uc_link_transmit.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_double,
                                    C.c_uint64, C.c_size_t, C.c_size_t, C.c_uint64, C.c_void_p]
     L.uc_link_noise_words.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_size_t, C.c_void_p, C.c_void_p]
-    _lib = L
-    return L
 
 
-def _check(rc, what):
-    if rc < 0:
-        msg = lib().uc_link_last_error()
-        raise LinkError("%s failed (rc=%d): %s" % (what, rc, msg.decode() if msg else ""))
-    return rc
+_so = Binding("link", LinkError, _declare)
+LIB_PATH, build, lib, _check = _so.path, _so.build, _so.lib, _so.check
 
 
 def default_config(**over):

@@ -14,15 +14,11 @@ where the microphone hears the sound `delay_samples + slope * j` later than the 
 `undo` gives the line of a row rendered by the link's law; `drift` estimates lines from a recording.
 """
 import ctypes as C
-import os
-import subprocess
 from fractions import Fraction
 
 import numpy as np
 
-_PKG = os.path.dirname(os.path.abspath(__file__))
-_ROOT = os.path.dirname(_PKG)  # ultrasonic-communication_amd/
-LIB_PATH = os.environ.get("UCHIRP_RETIME_LIB") or os.path.join(_ROOT, "libuchirp_retime.so")  # UCHIRP_RETIME_LIB: diagnostic builds
+from ._binding import Binding
 
 ABI_VERSION = 1
 DTYPE_I32, DTYPE_F32 = 0, 1
@@ -47,52 +43,16 @@ class RetimeError(RuntimeError):
     pass
 
 
-def build(force=False):
-    """Compile libuchirp_retime.so for gfx950 with hipcc (in-tree)."""
-    if os.environ.get("UCHIRP_RETIME_LIB"):    # a diagnostic build named by the caller: it is what it is
-        return LIB_PATH
-    if force or not os.path.exists(LIB_PATH):
-        subprocess.check_call(["make", "-C", _ROOT] + (["-B"] if force else []) + ["libuchirp_retime.so"])
-    else:
-        subprocess.check_call(["make", "-C", _ROOT, "libuchirp_retime.so"], stdout=subprocess.DEVNULL)
-    return LIB_PATH
-
-
-_lib = None
-
-
-def lib():
-    """Load libuchirp_retime.so; raises RetimeError if it is absent (no fallback)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    # one process, ONE HIP runtime: torch's bundled libamdhip64 first (see uchirp.lib())
-    try:
-        import torch  # noqa: F401
-    except ImportError:
-        pass
-    if not os.path.exists(LIB_PATH):
-        raise RetimeError("libuchirp_retime.so not built: run `make -C %s libuchirp_retime.so` (hipcc, gfx950); "
-                          "there is no CPU fallback" % _ROOT)
-    L = C.CDLL(LIB_PATH)
-    L.uc_retime_abi_version.restype = C.c_int
-    L.uc_retime_last_error.restype = C.c_char_p
+def _declare(L):
     L.uc_retime_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-    L.uc_retime_destroy.argtypes = [C.c_void_p]
-    L.uc_retime_destroy.restype = None
     L.uc_retime_fixed.argtypes = [C.c_double, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.uc_retime_table.argtypes = [C.POINTER(C.c_float)]
     L.uc_retime_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_uint64, C.c_size_t, C.c_size_t, C.c_void_p,
                                  C.c_size_t, C.c_void_p, C.c_uint64, C.c_size_t, C.c_size_t, C.c_void_p]
-    _lib = L
-    return L
 
 
-def _check(rc, what):
-    if rc < 0:
-        msg = lib().uc_retime_last_error()
-        raise RetimeError("%s failed (rc=%d): %s" % (what, rc, msg.decode() if msg else ""))
-    return rc
+_so = Binding("retime", RetimeError, _declare, env="UCHIRP_RETIME_LIB")  # UCHIRP_RETIME_LIB: diagnostic builds
+LIB_PATH, build, lib, _check = _so.path, _so.build, _so.lib, _so.check
 
 
 def fixed(delay, slope=0.0):

@@ -12,17 +12,12 @@ A scene is written as
 `model` is the same definition in numpy / float64, built from `link.signal` and `link.normals`.
 """
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 from . import link
 from .link import DTYPE_F32, DTYPE_I16, DTYPE_I32, MAX_TEXT, LinkConfig, convert  # noqa: F401  (one set of formats)
-
-_PKG = os.path.dirname(os.path.abspath(__file__))
-_ROOT = os.path.dirname(_PKG)  # ultrasonic-communication_amd/
-LIB_PATH = os.path.join(_ROOT, "libuchirp_scene.so")
+from ._binding import Binding
 
 ABI_VERSION = 1
 MAX_PATHS = 16
@@ -48,50 +43,16 @@ class SceneError(RuntimeError):
     pass
 
 
-def build(force=False):
-    """Compile libuchirp_scene.so for gfx950 with hipcc (in-tree)."""
-    if force or not os.path.exists(LIB_PATH):
-        subprocess.check_call(["make", "-C", _ROOT] + (["-B"] if force else []) + ["libuchirp_scene.so"])
-    else:
-        subprocess.check_call(["make", "-C", _ROOT, "libuchirp_scene.so"], stdout=subprocess.DEVNULL)
-    return LIB_PATH
-
-
-_lib = None
-
-
-def lib():
-    """Load libuchirp_scene.so; raises SceneError if it is absent (no fallback)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    # one process, ONE HIP runtime: torch's bundled libamdhip64 first (see uchirp.lib())
-    try:
-        import torch  # noqa: F401
-    except ImportError:
-        pass
-    if not os.path.exists(LIB_PATH):
-        raise SceneError("libuchirp_scene.so not built: run `make -C %s libuchirp_scene.so` (hipcc, gfx950); "
-                         "there is no CPU fallback" % _ROOT)
-    L = C.CDLL(LIB_PATH)
-    L.uc_scene_abi_version.restype = C.c_int
-    L.uc_scene_last_error.restype = C.c_char_p
+def _declare(L):
     L.uc_scene_default_config.argtypes = [C.POINTER(LinkConfig)]
     L.uc_scene_create.argtypes = [C.c_int, C.POINTER(LinkConfig), C.POINTER(C.c_void_p)]
-    L.uc_scene_destroy.argtypes = [C.c_void_p]
-    L.uc_scene_destroy.restype = None
     L.uc_scene_render.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
                                   C.c_size_t, C.c_void_p, C.c_int, C.c_double, C.c_uint64, C.c_size_t, C.c_size_t, C.c_uint64,
                                   C.c_void_p]
-    _lib = L
-    return L
 
 
-def _check(rc, what):
-    if rc < 0:
-        msg = lib().uc_scene_last_error()
-        raise SceneError("%s failed (rc=%d): %s" % (what, rc, msg.decode() if msg else ""))
-    return rc
+_so = Binding("scene", SceneError, _declare)
+LIB_PATH, build, lib, _check = _so.path, _so.build, _so.lib, _so.check
 
 
 def default_config(**over):

@@ -11,16 +11,11 @@ There is no CPU path behind `Tracker`; `finish`, `finish_model`, `select_model` 
 Arrays are written as in uchirp.xcorr: [[row, row, ...], ...], the first row of an array its reference.
 """
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 from . import retime, xcorr
-
-_PKG = os.path.dirname(os.path.abspath(__file__))
-_ROOT = os.path.dirname(_PKG)  # ultrasonic-communication_amd/
-LIB_PATH = os.environ.get("UCHIRP_TRACK_LIB") or os.path.join(_ROOT, "libuchirp_track.so")  # UCHIRP_TRACK_LIB: diagnostic builds
+from ._binding import Binding
 
 ABI_VERSION = 1
 DTYPE_I32, DTYPE_F32 = 0, 1
@@ -66,52 +61,16 @@ class TrackError(RuntimeError):
     pass
 
 
-def build(force=False):
-    """Compile libuchirp_track.so for gfx950 with hipcc (in-tree)."""
-    if os.environ.get("UCHIRP_TRACK_LIB"):    # a diagnostic build named by the caller: it is what it is
-        return LIB_PATH
-    if force or not os.path.exists(LIB_PATH):
-        subprocess.check_call(["make", "-C", _ROOT] + (["-B"] if force else []) + ["libuchirp_track.so"])
-    else:
-        subprocess.check_call(["make", "-C", _ROOT, "libuchirp_track.so"], stdout=subprocess.DEVNULL)
-    return LIB_PATH
-
-
-_lib = None
-
-
-def lib():
-    """Load libuchirp_track.so; raises TrackError if it is absent (no fallback)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    # one process, ONE HIP runtime: torch's bundled libamdhip64 first (see uchirp.lib())
-    try:
-        import torch  # noqa: F401
-    except ImportError:
-        pass
-    if not os.path.exists(LIB_PATH):
-        raise TrackError("libuchirp_track.so not built: run `make -C %s libuchirp_track.so` (hipcc, gfx950); "
-                         "there is no CPU fallback" % _ROOT)
-    L = C.CDLL(LIB_PATH)
-    L.uc_track_abi_version.restype = C.c_int
-    L.uc_track_last_error.restype = C.c_char_p
+def _declare(L):
     L.uc_track_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-    L.uc_track_destroy.argtypes = [C.c_void_p]
-    L.uc_track_destroy.restype = None
     L.uc_track_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t,
                                    C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p,
                                    C.c_void_p]
     L.uc_track_finish.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
-    _lib = L
-    return L
 
 
-def _check(rc, what):
-    if rc < 0:
-        msg = lib().uc_track_last_error()
-        raise TrackError("%s failed (rc=%d): %s" % (what, rc, msg.decode() if msg else ""))
-    return rc
+_so = Binding("track", TrackError, _declare, env="UCHIRP_TRACK_LIB")  # UCHIRP_TRACK_LIB: diagnostic builds
+LIB_PATH, build, lib, _check = _so.path, _so.build, _so.lib, _so.check
 
 
 def _record(p):

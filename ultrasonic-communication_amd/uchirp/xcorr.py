@@ -12,14 +12,12 @@ Arrays are written as
 and a delay is the number of samples by which a microphone hears the sound LATER than its array's reference.
 """
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-_PKG = os.path.dirname(os.path.abspath(__file__))
-_ROOT = os.path.dirname(_PKG)  # ultrasonic-communication_amd/
-LIB_PATH = os.environ.get("UCHIRP_XCORR_LIB") or os.path.join(_ROOT, "libuchirp_xcorr.so")  # UCHIRP_XCORR_LIB: diagnostic builds
+from . import align
+from ._binding import Binding
+from .align import PAIR_DTYPE, _arrays, _pairs, _record, _split  # noqa: F401  (one layout of pairs, one shape of records)
 
 ABI_VERSION = 1
 DTYPE_I32, DTYPE_F32 = 0, 1
@@ -43,62 +41,19 @@ class XcorrPeak(C.Structure):
                 ("flags", C.c_uint32)]
 
 
-PAIR_DTYPE = np.dtype([("ref", "<u4"), ("mic", "<u4")])
-
-
 class XcorrError(RuntimeError):
     pass
 
 
-def build(force=False):
-    """Compile libuchirp_xcorr.so for gfx950 with hipcc (in-tree)."""
-    if os.environ.get("UCHIRP_XCORR_LIB"):    # a diagnostic build named by the caller: it is what it is
-        return LIB_PATH
-    if force or not os.path.exists(LIB_PATH):
-        subprocess.check_call(["make", "-C", _ROOT] + (["-B"] if force else []) + ["libuchirp_xcorr.so"])
-    else:
-        subprocess.check_call(["make", "-C", _ROOT, "libuchirp_xcorr.so"], stdout=subprocess.DEVNULL)
-    return LIB_PATH
-
-
-_lib = None
-
-
-def lib():
-    """Load libuchirp_xcorr.so; raises XcorrError if it is absent (no fallback)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    # one process, ONE HIP runtime: torch's bundled libamdhip64 first (see uchirp.lib())
-    try:
-        import torch  # noqa: F401
-    except ImportError:
-        pass
-    if not os.path.exists(LIB_PATH):
-        raise XcorrError("libuchirp_xcorr.so not built: run `make -C %s libuchirp_xcorr.so` (hipcc, gfx950); "
-                         "there is no CPU fallback" % _ROOT)
-    L = C.CDLL(LIB_PATH)
-    L.uc_xcorr_abi_version.restype = C.c_int
-    L.uc_xcorr_last_error.restype = C.c_char_p
+def _declare(L):
     L.uc_xcorr_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-    L.uc_xcorr_destroy.argtypes = [C.c_void_p]
-    L.uc_xcorr_destroy.restype = None
     L.uc_xcorr_correlate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t,
                                      C.c_size_t, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]
     L.uc_xcorr_peak.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(XcorrPeak)]
-    _lib = L
-    return L
 
 
-def _check(rc, what):
-    if rc < 0:
-        msg = lib().uc_xcorr_last_error()
-        raise XcorrError("%s failed (rc=%d): %s" % (what, rc, msg.decode() if msg else ""))
-    return rc
-
-
-def _record(delay, height, runner_up, lag, flags):
-    return {"delay_samples": float(delay), "height": float(height), "runner_up": float(runner_up), "lag": int(lag), "flags": int(flags)}
+_so = Binding("xcorr", XcorrError, _declare, env="UCHIRP_XCORR_LIB")  # UCHIRP_XCORR_LIB: diagnostic builds
+LIB_PATH, build, lib, _check = _so.path, _so.build, _so.lib, _so.check
 
 
 def peak(row):
@@ -114,38 +69,7 @@ def peak(row):
 
 def peak_model(row):
     """The peak rule of include/uchirp_xcorr.h (that of uchirp_align.h) in numpy / float64: the same record as `peak`."""
-    r = np.asarray(row, np.float64)
-    if r.ndim != 1 or len(r) < 3 or len(r) % 2 == 0:
-        raise ValueError("a correlation row has 2 L + 1 values")
-    L = (len(r) - 1) // 2
-    if not 1 <= L <= MAX_LAG or not np.isfinite(r).all():
-        raise ValueError("L must be 1 .. %d and every value finite" % MAX_LAG)
-    flags = AT_EDGE if int(np.argmax(r)) in (0, 2 * L) else 0
-    heights = []
-    for k in range(1, 2 * L):
-        if r[k] > 0.0 and r[k] >= r[k - 1] and r[k] > r[k + 1]:
-            c = (r[k - 1] + r[k + 1]) / (2.0 * r[k])
-            if -1.0 < c < 1.0:
-                w = np.arccos(c)
-                q = (r[k + 1] - r[k - 1]) / (2.0 * np.sin(w))
-                heights.append((float(np.hypot(r[k], q)), k, float(np.arctan2(q, r[k]) / w)))
-            else:
-                heights.append((float(r[k]), k, 0.0))
-    if not heights:
-        return _record(0.0, 0.0, 0.0, 0, flags | NO_PEAK)
-    best = max(range(len(heights)), key=lambda i: (heights[i][0], -i))        # the first one on a tie
-    h, k, d = heights[best]
-    others = [heights[i][0] for i in range(len(heights)) if i != best]
-    return _record(k - L + d, h, max(others) / h if others else 0.0, k - L, flags)
-
-
-def _pairs(pairs):
-    p = np.asarray(pairs, np.int64).reshape(-1, 2)
-    if len(p) == 0 or p.min() < 0 or p.max() > 0xFFFFFFFF:
-        raise ValueError("pairs: a non-empty list of (ref, mic) rows")
-    out = np.zeros(len(p), PAIR_DTYPE)
-    out["ref"], out["mic"] = p[:, 0], p[:, 1]
-    return out
+    return align.peak_model(row, MAX_LAG)
 
 
 def _rows(x, first, n, max_lag):
@@ -225,13 +149,6 @@ def emulate32(x, pairs, first=0, n=None, max_lag=512):
     return out
 
 
-def _arrays(arrays):
-    arrays = [[int(m) for m in a] for a in arrays]
-    if not arrays or any(len(a) < 2 for a in arrays):
-        raise ValueError("every array needs a reference and at least one more microphone")
-    return arrays, [(a[0], m) for a in arrays for m in a[1:]]
-
-
 class Xcorr:
     """One uc_xcorr: the wide-lag correlator on one MI355X."""
 
@@ -292,20 +209,9 @@ class Xcorr:
         return _split(arrays, [peak(r) for r in rows])
 
 
-def _split(arrays, records):
-    delays, peaks, at = [], [], 0
-    for a in arrays:
-        recs = records[at:at + len(a) - 1]
-        at += len(a) - 1
-        delays.append([0.0] + [r["delay_samples"] for r in recs])
-        peaks.append([None] + recs)
-    return delays, peaks
-
-
 def delays_model(x, arrays, first=0, n=None, max_lag=512):
     """`Xcorr.delays` through `model` and `peak_model`: float64 on the host."""
-    arrays, pairs = _arrays(arrays)
-    return _split(arrays, [peak_model(r) for r in model(x, pairs, first, n, max_lag)])
+    return align.delays_model(x, arrays, first, n, max_lag, model, peak_model)
 
 
 def steer(x, arrays, xcorr=None, first=0, n=None, max_lag=512, stream=None):
