@@ -1,5 +1,5 @@
 """uchirp._binding -- the one ctypes loader behind the sibling libraries' modules (link, scene, array, align, xcorr, retime,
-track): where libuchirp_<name>.so lies, how it is built, how it is loaded into a process that torch may share, and how a
+track, rate): where libuchirp_<name>.so lies, how it is built, how it is loaded into a process that torch may share, and how a
 negative return code becomes the module's exception.  A module keeps its public names by taking them from its Binding
     _so = Binding("align", AlignError, _declare, env="UCHIRP_ALIGN_LIB")
     LIB_PATH, build, lib, _check = _so.path, _so.build, _so.lib, _so.check
