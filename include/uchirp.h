@@ -210,6 +210,21 @@ int uc_process_batch(uc_ctx* ctx, const void* frames, int dtype,
  * passing the hand-out's exit, and the next launch on that counter would silently skip frame groups. */
 int uc_debug_busy_counters(uc_ctx* ctx);
 
+/* Diagnostic (tests): the (up, down) mag_max records that the LAST band launch of uc_receive_streams (st == NULL: the
+ * context's scratch) or of uc_receive_streams_next (st) wrote: out[(s * units + u) * 2 + {0, 1}], u = jb * 8 + (m - 1) --
+ * block jb of the call (with a busy mask: the jb-th ACCEPTED block; rows beyond a stream's accepted count are stale),
+ * FIFO offset m = 1 .. 8: the frame that ends 256 m samples into block jb and begins in the block in front of it.  A call
+ * served block by block leaves the records of its last step (units = 8).  A one-block call of a live state evaluates only
+ * the offsets main()'s switch can still look at: the components it passes over read +0.  A frame that holds a NaN sample
+ * gives NaN in both components.
+ * Waits for that call's stream.  out: host memory.  Changes nothing: a receiver call after it continues as before.
+ * Returns the number of float pairs, or < 0: -EINVAL (NULL or foreign arguments, cap_pairs too small; *n_streams and
+ * *units are still filled in when the shape is known), -ENODATA (no call with whole blocks yet), -ENOTSUP (that call's
+ * stream is being captured). */
+struct uc_rx_state;
+int uc_debug_rx_records(uc_ctx* ctx, struct uc_rx_state* st /*nullable*/, float* out, size_t cap_pairs,
+                        size_t* n_streams /*nullable*/, size_t* units /*nullable*/);
+
 /* number of uc_stats records uc_process_batch writes per frame (1 or 2) */
 int uc_stats_per_frame(const uc_ctx* ctx);
 

@@ -5,6 +5,7 @@
 // FIFO bounds asserted on every call (quirk Q8), the partition / span arithmetic of the multi-GPU leg at its edges, the
 // multiply-high divisor, and the argument checks of the C-ABI that come before any device call.
 #include <cassert>
+#include <cerrno>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -248,6 +249,12 @@ int main() {
     CHECK(uc_group_unique_id(nullptr, 0) < 0);
     CHECK(uc_clock_probe(nullptr, 1) < 0 && uc_clock_read(nullptr, nullptr) < 0 && uc_clock_stamps(nullptr, nullptr, 0) < 0);
     CHECK(uc_debug_busy_counters(nullptr) < 0);
+    {
+      float pairs[4] = {0, 0, 0, 0};
+      size_t ns = 7, units = 7;
+      CHECK(uc_debug_rx_records(nullptr, nullptr, pairs, 2, &ns, &units) == -EINVAL && ns == 0 && units == 0 && pairs[0] == 0.f);
+      CHECK(uc_debug_rx_records(nullptr, nullptr, nullptr, 0, nullptr, nullptr) == -EINVAL);
+    }
     CHECK(uc_device_malloc(0, 16, nullptr) < 0);
     CHECK(uc_abi_version() == UC_ABI_VERSION);
   }

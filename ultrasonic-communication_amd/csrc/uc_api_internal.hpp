@@ -75,7 +75,12 @@ struct RxScratch {
   // for streams WITHOUT a state also what a state would carry from step to step -- the 9 surviving records, main()'s locals, the
   // need words
   DevBuf fill, carry, loop, need;
+  // uc_debug_rx_records: the shape of the last band launch into `rec` ([rec_streams][rec_units] records; 0: none yet) and the
+  // stream it went to
+  size_t rec_streams = 0, rec_units = 0;
+  hipStream_t rec_stream = nullptr;
   void release() {
+    rec_streams = rec_units = 0;
     for (DevBuf* b : {&in, &busy, &acc, &na, &pad, &rec, &text, &ntext, &trace, &ntrace, &pcm, &hist, &fill, &carry, &loop, &need})
       b->release();
   }

@@ -328,6 +328,7 @@ static int receive_streams_impl(uc_ctx* c, uc_rx_state* st, const void* samples,
     const size_t n_frames = n_streams * nb * per_block;
     // (every scratch buffer of the call is sized before its first launch: a call that cannot be served -- out of memory, or a
     // capture that would have to allocate -- has enqueued nothing)
+    sc.rec_streams = sc.rec_units = 0;  // (uc_debug_rx_records: nothing to read until this call's band launch is enqueued)
     if (int rc = sc.rec.ensure(n_frames * sizeof(float2))) return rc;
     // a call of several blocks without a busy mask is served block by block when a step fills the chip (receive_steps)
     const size_t step_min = c->rx_step_min >= 0 ? (size_t)c->rx_step_min : (c->cfg.variant == UC_SYNC_CPLX ? 1024u : 8192u);
@@ -492,6 +493,9 @@ static int receive_streams_impl(uc_ctx* c, uc_rx_state* st, const void* samples,
     lrc = uc::launch_rx_replay(rp, stream);
     if (lrc != (int)hipSuccess) return hip_fail((hipError_t)lrc, "rx replay kernel launch");
     }
+    sc.rec_streams = n_streams;
+    sc.rec_units = stepped ? per_block : nb * per_block;  // (block by block: every step writes its 8 records per stream over the last one's)
+    sc.rec_stream = stream;
     if (st) {
       st->blocks_seen += nb;
       st->dtype = dtype_in;
@@ -531,6 +535,34 @@ extern "C" int uc_receive_streams(uc_ctx* c, const void* samples, int dtype, siz
                                   void* hip_stream) {
   return receive_streams_impl(c, nullptr, samples, dtype, n_streams, n_samples, stream_stride_elems, busy, text, text_cap, n_text,
                               trace, trace_cap, n_trace, hip_stream);
+}
+
+// Diagnostic (tests): what the last band launch of a receiver call left in RxScratch::rec -- the only numbers of the ROWS build of
+// the band kernel that anything outside the library can see.  Reads, waits, copies; touches no state.
+extern "C" int uc_debug_rx_records(uc_ctx* c, uc_rx_state* st, float* out, size_t cap_pairs, size_t* n_streams, size_t* units) {
+  if (n_streams) *n_streams = 0;
+  if (units) *units = 0;
+  if (!c) return fail(-EINVAL, "uc_debug_rx_records: NULL ctx");
+  if (st && st->c != c) return fail(-EINVAL, "uc_debug_rx_records: the state belongs to another context");
+  const RxScratch& sc = st ? st->rx : c->rx;
+  if (sc.rec_streams == 0 || sc.rec_units == 0 || !sc.rec.p)
+    return fail(-ENODATA, "uc_debug_rx_records: no receiver call with whole blocks has run on this %s yet", st ? "state" : "context");
+  const size_t pairs = sc.rec_streams * sc.rec_units;
+  if (n_streams) *n_streams = sc.rec_streams;
+  if (units) *units = sc.rec_units;
+  if (pairs >= ((size_t)1 << 31)) return fail(-EINVAL, "uc_debug_rx_records: too many records");
+  if (!out || cap_pairs < pairs) return fail(-EINVAL, "uc_debug_rx_records: room for %zu pairs, the call left %zu", out ? cap_pairs : (size_t)0, pairs);
+  hipError_t e = hipSetDevice(c->device);
+  if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (sc.rec_stream && (hipStreamIsCapturing(sc.rec_stream, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone)) {
+    (void)hipGetLastError();
+    return fail(-ENOTSUP, "uc_debug_rx_records: the stream of the last call is being captured");
+  }
+  e = hipStreamSynchronize(sc.rec_stream);
+  if (e == hipSuccess) e = hipMemcpy(out, sc.rec.p, pairs * sizeof(float2), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return hip_fail(e, "uc_debug_rx_records: copy back");
+  return (int)pairs;
 }
 
 // ---- live streams: the same call, chunk after chunk ----------------------------------------------------------------

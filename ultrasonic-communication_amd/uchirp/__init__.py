@@ -37,6 +37,7 @@ EXPORTS = ["uc_abi_version", "uc_last_error", "uc_default_config", "uc_create", 
            "uc_group_destroy", "uc_group_world", "uc_group_local_count", "uc_group_first_rank", "uc_group_ctx",
            "uc_group_process_batch", "uc_group_wait_gather", "uc_group_synchronize",
            "uc_device_count", "uc_device_malloc", "uc_device_free", "uc_device_copy", "uc_clock_probe", "uc_clock_read", "uc_clock_stamps", "uc_receive_streams", "uc_debug_busy_counters",
+           "uc_debug_rx_records",
            "uc_rx_state_create", "uc_rx_state_reset", "uc_rx_state_destroy", "uc_receive_streams_next",
            "uc_rx_state_streams", "uc_rx_state_keep_previous", "uc_group_receive_streams", "uc_group_receive_streams_next", "uc_group_process_stream",
            "uc_dfsdm_sinc5_streams", "uc_group_preflight"]
@@ -151,6 +152,8 @@ def lib():
     L.uc_receive_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p,
                                      C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     L.uc_debug_busy_counters.argtypes = [C.c_void_p]
+    if hasattr(L, "uc_debug_rx_records"):           # (UCHIRP_LIB may name an older diagnostic build)
+        L.uc_debug_rx_records.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.uc_rx_state_create.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
     L.uc_rx_state_reset.argtypes = [C.c_void_p, C.c_void_p]
     L.uc_rx_state_destroy.argtypes = [C.c_void_p]
@@ -224,6 +227,19 @@ class Engine:
     def busy_counters(self):
         """uc_debug_busy_counters: hand-out counter words left non-zero with nothing in flight (always 0)."""
         return _check(lib().uc_debug_busy_counters(self._h), "uc_debug_busy_counters")
+
+    def rx_records(self, state=None):
+        """uc_debug_rx_records -> float32 [n_streams, units, 2]: the (up, down) mag_max records the last band launch of
+        receive_many (state None) or of state.next() left, unit u = 8 jb + (m - 1) (waits for that call's stream)."""
+        h = state._h if state is not None else None
+        ns, units = C.c_size_t(), C.c_size_t()
+        rc = lib().uc_debug_rx_records(self._h, h, None, 0, C.byref(ns), C.byref(units))
+        if ns.value == 0:
+            _check(rc, "uc_debug_rx_records")
+        out = np.zeros((ns.value, units.value, 2), np.float32)
+        _check(lib().uc_debug_rx_records(self._h, h, out.ctypes.data_as(C.c_void_p), ns.value * units.value, C.byref(ns),
+                                         C.byref(units)), "uc_debug_rx_records")
+        return out
 
     def clock_probe(self, on=True):
         """uc_clock_probe: the following launches run the clock-stamped twin of their kernel (never time with it on)."""
@@ -357,14 +373,19 @@ class Engine:
             if stream is None:
                 stream = torch.cuda.current_stream(t.device).cuda_stream
         else:
-            a = np.ascontiguousarray(samples)
+            a = np.asarray(samples)
+            # (the first columns of a wider array with contiguous rows are read where they lie: stream_stride_elems > n_samples;
+            # PDM words are always handed over contiguous, as the DFSDM kernel's alignment rules want them)
+            if not (not pdm and a.ndim == 2 and a.shape[0] > 1 and a.shape[1] > 0 and a.strides[1] == a.itemsize and a.itemsize == 4
+                    and a.strides[0] % 4 == 0 and a.strides[0] >= a.shape[1] * 4):
+                a = np.ascontiguousarray(a)
             if pdm and a.dtype == np.uint32:
                 a = a.view(np.int32)
             if a.ndim != 2 or a.dtype not in (np.int32, np.float32):
                 raise TypeError("samples must be a 2-d int32 / float32 array")
             dt = DTYPE_I32 if a.dtype == np.int32 else DTYPE_F32
             ns, nsmp = a.shape
-            sstride = 0
+            sstride = a.strides[0] // 4 if ns > 1 and a.strides[0] != nsmp * 4 else 0
             ptr = a.ctypes.data_as(C.c_void_p)
         if pdm:
             if dt != DTYPE_I32:
