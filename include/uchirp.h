@@ -410,6 +410,13 @@ int uc_receive_streams_next(uc_ctx* ctx, uc_rx_state* st, const void* samples, i
  * exactly: output q belongs to input sample halo + q*D.
  * peaks (nullable): one record per overlap-save block b = q / hop: the largest compressed value
  * of the block (first one on ties) and its offset q - b*hop.
+ * Non-finite samples: the blocks are transformed whole, so a NaN or Inf sample makes EVERY output
+ * non-finite in each overlap-save block that reads it -- block b reads samples b*hop*D ..
+ * halo + ((b+1)*hop - 1)*D of the buffer: its own hop*D and the (L-1)*D + 26 in front of them, so a sample
+ * of that overlap spoils two blocks -- where the time-domain sum above loses only the about L outputs
+ * whose taps reach it.  Blocks that do not read the sample are unaffected, bit for bit.  A record's
+ * offset is always below the block's number of outputs; a block with no output that compares (all of
+ * them NaN) reports value = NaN, offset = 0: arm_max_f32's answer for a block whose first element is NaN.
  * `samples` must be 16-byte aligned when it is a device pointer.  Host or device pointers;
  * asynchronous on hip_stream with device pointers; fixed shapes, so the call can be captured
  * into a hipGraph and replayed chunk after chunk.

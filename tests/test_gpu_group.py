@@ -293,5 +293,14 @@ def test_group_process_stream_of_one_device_equals_the_engine(uchirp):
     assert np.array_equal(ph.view(np.uint8), want_pk.view(np.uint8)) and np.array_equal(ch.view(np.uint32), want.view(np.uint32))
     g.process_stream([x], x.size, [ph])                                # peaks only
     assert np.array_equal(ph.view(np.uint8), want_pk.view(np.uint8))
+    # a NaN sample that only block 3 reads (include/uchirp.h): that block's record is (NaN, 0) through the group as well,
+    # and everything is the engine's, bit for bit
+    xn = x.copy()
+    xn[halo + 8 * 3 * hop + 100] = np.nan
+    wn, wn_pk = eng.process_stream(xn)
+    g.process_stream([xn], xn.size, [ph], compressed=[ch])
+    assert np.array_equal(ph.view(np.uint8), wn_pk.view(np.uint8)) and np.array_equal(ch.view(np.uint32), wn.view(np.uint32))
+    assert np.isnan(ph["value"][3]) and ph["offset"][3] == 0 and (ph["offset"] < hop).all()
+    assert np.isnan(ch[3 * hop:4 * hop]).all() and np.isfinite(ch[:3 * hop]).all() and np.isfinite(ch[4 * hop:]).all()
     g.close()
     eng.close()

@@ -329,9 +329,13 @@ __global__ __launch_bounds__(T, 2) void stream_kernel(const StreamParams p) {
         const float v0 = red[0], v1 = red[2];
         const int i0 = __float_as_int(red[1]), i1 = __float_as_int(red[3]);
         const bool second = v1 > v0 || (v1 == v0 && i1 < i0);
+        const int wi01 = second ? i1 : i0;
+        // no output of the block compared (every one is NaN: a non-finite sample, include/uchirp.h): arm_max_f32's answer
+        // for a block whose first element is NaN -- that NaN, index 0 -- and never an offset outside the block
+        const bool none = wi01 == 0x7fffffff;
         uc_peak pk;
-        pk.value = __builtin_sqrtf(second ? v1 : v0);
-        pk.offset = (uint32_t)(second ? i1 : i0);
+        pk.value = none ? __int_as_float(0x7fc00000) : __builtin_sqrtf(second ? v1 : v0);
+        pk.offset = none ? 0u : (uint32_t)wi01;
         p.peaks[b] = pk;
       }
     }
