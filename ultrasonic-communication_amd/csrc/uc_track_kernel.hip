@@ -5,12 +5,9 @@
 // track_kernel.  The work unit is (pair, window, group of GROUP segments), numbered window-major inside a pair so that
 // units which read the same samples are neighbours; units are dealt statically, a contiguous range each, to the 2-wave
 // workgroups of a persistent grid, and a workgroup does a unit from its first load to its 2 L + 1 stored sums on its own:
-// no atomics, and a sum cannot depend on the grid.  A unit is computed by the passes of uc_xcorr_kernel.hip in that kernel's order and with its barrier
-// discipline -- pk_dft16 | xf_store1 | xf_fwd2 | xf_fwd3<true> for a_s and for b_s, pk_cfmac into sixteen resident
-// accumulators, xf_invA | xf_invB | xf_invC<false> -- so that a unit sum has the bits that kernel gives for first' =
-// first + w hop and n' = window_len.  The comments there on why the two transforms are kept apart, on which tile a pass may
-// write behind which barrier and on the buffer resources that cover exactly the samples that exist hold here word for word.
-// What is new:
+// no atomics, and a sum cannot depend on the grid.  A unit is the unit of uc_corr_unit.hpp, the code xcorr_kernel runs,
+// over the window first' = first + w hop, n' = window_len: that is why a unit sum has the bits that kernel gives.
+// What is this kernel's own:
 //   - a unit carries its window's first sample;
 //   - a window's last group is usually short (window_len = 8192 at L = 128 is 4 + 1 segments), so the units are of unequal
 //     length and a workgroup's next unit starts often;
@@ -19,50 +16,27 @@
 //     registers are the accumulators' and the za's, both dead by then).
 //
 // track_crest_kernel.  One wave per (pair, window).  The lanes stride over k: each adds the row's unit sums in double in
-// ascending group order (what xcorr_sum_kernel does), stores the double if corr is given and keeps it in LDS; the largest
-// sample (the first one on a tie) and the test for values that are not finite ride along.  Then every lane walks its
-// candidates and keeps its own best four by (h2 descending, k ascending) in registers; four rounds of a wave-wide
-// butterfly pick the best remaining head, and the four winners are written in ascending k.  The order is total (a k
-// belongs to one lane), so the result depends neither on the grid nor on which lane saw which k.
+// ascending group order (corr_unit_sum, what xcorr_sum_kernel does), stores the double if corr is given and keeps it in
+// LDS; the largest sample (the first one on a tie) and the test for values that are not finite ride along.  Then every
+// lane walks its candidates and keeps its own best four by (h2 descending, k ascending) in registers; four rounds of a
+// wave-wide butterfly pick the best remaining head, and the four winners are written in ascending k.  The order is total
+// (a k belongs to one lane), so the result depends neither on the grid nor on which lane saw which k.
 #include <hip/hip_runtime.h>
 
-#include "uc_dev.hpp"
+#include "uc_corr_unit.hpp"
 #include "uc_track.hpp"
-#include "uc_xform.hpp"
-#include "uc_xform_split.hpp"
 
 namespace uc_track_dev {
 namespace {
 
 using namespace uc;
 
-constexpr int T = THREADS;
-constexpr int kTw2Off = 4 * POINTS;              // floats: behind the two tiles of 2048 complex values
-constexpr int kTwBOff = kTw2Off + kXfTw2Floats;
-constexpr int kLdsFloats = kTwBOff + kXfTwBFloats;
-
-static_assert(POINTS == kN && THREADS == kXfThreads, "the transform of uc_xform.hpp");
-static_assert(2 * MAX_LAG + 1 <= 9 * THREADS, "outputs j + 128 t, t = 0 .. 8, hold every lag");
+static_assert(POINTS == kN && THREADS == kXfThreads && 2 * MAX_LAG + 1 <= kCorrMaxLags, "the unit of uc_corr_unit.hpp");
 static_assert(sizeof(Slot) == 32 && sizeof(Crest) == 8 + 32 * SLOTS, "struct uc_track_crest");
 
-template <int DT>
-__device__ __forceinline__ float as_sample(float raw) {
-  return DT == DT_I32 ? (float)__float_as_int(raw) : raw;
-}
-
-constexpr int kNowhere = 0x7ffffff0;   // a byte offset beyond every window (a window has at most 8192 bytes)
-
-// the raw words of one segment: a_s[j + 128 t] and b_s[j + 128 t]
-struct Raw {
-  float a[16];
-  float b[16];
-};
-
-// one unit: its rows, its window and its segments (workgroup-uniform)
+// one unit: its window and its segments (workgroup-uniform)
 struct Unit {
-  const uint32_t* ref;
-  const uint32_t* mic;
-  int64_t first;      // the window's first reference sample
+  CorrWindow w;
   uint32_t seg0, seg1;
 };
 
@@ -74,63 +48,22 @@ __device__ __forceinline__ Unit unit_of(const Params& p, const Pair* __restrict_
   const uint32_t w = pw - pair * p.n_windows;
   const Pair pr = pairs[pair];
   Unit u;
-  u.ref = (const uint32_t*)p.in + pr.ref;
-  u.mic = (const uint32_t*)p.in + pr.mic;
-  u.first = p.first + (int64_t)w * p.hop;
+  u.w.ref = (const uint32_t*)p.in + pr.ref;
+  u.w.mic = (const uint32_t*)p.in + pr.mic;
+  u.w.first = p.first + (int64_t)w * p.hop;
+  u.w.n = p.window_len;
+  u.w.n_in = p.n_in;
   u.seg0 = grp * GROUP;
   u.seg1 = u.seg0 + GROUP < p.n_segments ? u.seg0 + GROUP : p.n_segments;   // > seg0
   return u;
 }
 
-// segment `seg` of the unit's window; S = POINTS - 2 L
-__device__ __forceinline__ void load_segment(const Params& p, const Unit& u, uint32_t seg, int S, int L, int j, Raw& g) {
-  const int64_t i0 = (int64_t)seg * S;                                  // from the window's first sample
-  const int64_t rest = p.window_len - i0;
-  const int cnt = rest < S ? (int)rest : S;                             // >= 1
-  const int64_t w0 = u.first + i0 - L;                                  // row element of b_s[0]; >= -L
-  const int lo = w0 < 0 ? (int)-w0 : 0;                                 // window index of the first sample inside the row
-  const int64_t room = p.n_in - w0;                                     // window indices below it lie inside the row; > lo
-  const int hi = room < cnt + 2 * L ? (int)room : cnt + 2 * L;          // > lo
-  const __amdgpu_buffer_rsrc_t ra = make_rsrc(u.ref + (u.first + i0), cnt * 4);
-  const __amdgpu_buffer_rsrc_t rb = make_rsrc(u.mic + (w0 + lo), (hi - lo) * 4);
-  // every offset whole in the vector operand: the range check looks at it
-#pragma unroll
-  for (int t = 0; t < 16; t++) g.a[t] = buf_ld32(ra, (j + T * t) * 4, 0);
-  if (lo == 0) {                                                        // (workgroup-uniform; all but a row's first samples)
-#pragma unroll
-    for (int t = 0; t < 16; t++) g.b[t] = buf_ld32(rb, (j + T * t) * 4, 0);
-  } else {
-    // the window starts in front of the row: the resource starts at the row, and a sample in front of it gets an offset
-    // that no resource holds
-#pragma unroll
-    for (int t = 0; t < 16; t++) {
-      const int e = j + T * t - lo;
-      g.b[t] = buf_ld32(rb, e < 0 ? kNowhere : e * 4, 0);
-    }
-  }
-}
-
 template <int DT>
-__global__ __launch_bounds__(T, 2) void track_kernel(const Params p, const Pair* __restrict__ pairs) {
-  __shared__ __attribute__((aligned(16))) float lds[kLdsFloats];
-  float* const cur = lds;               // the tile a pass 1 (and inverse pass A) writes
-  float* const oth = lds + 2 * POINTS;  // the tile a pass 2 (and inverse pass B) writes
-  float* tw2t = lds + kTw2Off;    // W_256^(t k): forward pass 2
-  float* twBt = lds + kTwBOff;    // W_128^(t k): inverse pass B
-
+__global__ __launch_bounds__(THREADS, 2) void track_kernel(const Params p, const Pair* __restrict__ pairs) {
+  __shared__ __attribute__((aligned(16))) float lds[kCorrLdsFloats];
   const int j = threadIdx.x;
-  const v2f K = mkv(kCos8, kSin8), H = mkv(kSqrtHalfF, kSqrtHalfF);
-  const __amdgpu_buffer_rsrc_t rs_tw = make_rsrc(p.tw, POINTS * 8);
-  const v2f t3a = buf_ld64(rs_tw, (j & (POINTS - 1)) * 8, 0);        // W_2048^j
-  const v2f t3b = buf_ld64(rs_tw, ((2 * j) & (POINTS - 1)) * 8, 0);  // W_2048^2j
-  const v2f t3c = buf_ld64(rs_tw, ((4 * j) & (POINTS - 1)) * 8, 0);  // W_2048^4j
-  xf_fill_twiddle_tables(tw2t, twBt, rs_tw, j);                      // (read behind the first barrier of the loop)
-  const XfAddr xa = xf_addresses(j);
-  // the pass-3 twiddles are used by every segment and stay resident; the pass-C ones are used once per unit and are
-  // derived there
-  v2f w3r[2][8];
-  xf_twiddles3(w3r[0], 0, t3a, t3b, t3c, K, H);
-  xf_twiddles3(w3r[1], 1, t3a, t3b, t3c, K, H);
+  CorrCtx c;
+  corr_setup(c, lds, p.tw, j);
 
   const int L = p.max_lag, S = POINTS - 2 * L, lags = 2 * L + 1;
   // this workgroup's units: one contiguous range of the numbering, all ranges within one unit of the same length.  (Dealing
@@ -140,76 +73,24 @@ __global__ __launch_bounds__(T, 2) void track_kernel(const Params p, const Pair*
   const uint32_t end = (uint32_t)(((uint64_t)blockIdx.x + 1) * p.n_units / gridDim.x);
   if (unit >= end) return;                                           // (the host launches no more workgroups than units)
   Unit u = unit_of(p, pairs, unit);
-  Raw g;
-  load_segment(p, u, u.seg0, S, L, j, g);
+  CorrRaw g;
+  corr_load_segment(u.w, u.seg0, S, L, j, g);
   for (;;) {
     const uint32_t next = unit + 1;
     const bool more = next < end;                                    // workgroup-uniform
     v2f acc[2][8];
-#pragma unroll
-    for (int h = 0; h < 2; h++)
-#pragma unroll
-      for (int t = 0; t < 8; t++) acc[h][t] = mkv(0.0f, 0.0f);
-    for (uint32_t seg = u.seg0; seg < u.seg1; ++seg) {
-      // ---- A_s: forward transform of a_s (registers -> cur -> oth -> registers)
-      v2f za[2][8];                                          // A_s[j + 128 h + 256 t]
-      {
-        v2f v[16];
-#pragma unroll
-        for (int t = 0; t < 16; t++) v[t] = mkv(as_sample<DT>(g.a[t]), 0.0f);
-        pk_dft16(v, K, H);
-        xf_store1(cur, xa, xa.s1, v);
-      }
-      __syncthreads();
-      xf_fwd2(cur, oth, tw2t, xa, j, K, H);
-      __syncthreads();
-#pragma unroll
-      for (int h = 0; h < 2; h++) xf_fwd3<true>(oth, za[h], h, w3r[h], t3a, t3b, t3c, j, K, H);
-      // ---- B_s: the same of b_s; pass 1 writes the tile pass 2 has read in front of the last barrier, pass 2 the tile pass 3
-      // has read in front of the barrier between them
-      {
-        v2f v[16];
-#pragma unroll
-        for (int t = 0; t < 16; t++) v[t] = mkv(as_sample<DT>(g.b[t]), 0.0f);
+    corr_clear(acc);
+    for (uint32_t seg = u.seg0; seg < u.seg1; ++seg)
+      corr_segment<DT == DT_I32>(c, g, acc, [&]() __attribute__((always_inline)) {
         // a whole transform ahead: the unit's next segment, or across the unit boundary the next unit's first one
         const bool inside = seg + 1 < u.seg1;
         if (inside || more) {                                // (workgroup-uniform)
           // (the next unit is derived again behind this one: that is cheaper than keeping it)
           const Unit ul = inside ? u : unit_of(p, pairs, next);
-          load_segment(p, ul, inside ? seg + 1 : ul.seg0, S, L, j, g);
+          corr_load_segment(ul.w, inside ? seg + 1 : ul.seg0, S, L, j, g);
         }
-        pk_dft16(v, K, H);
-        xf_store1(cur, xa, xa.s1, v);
-      }
-      __syncthreads();
-      xf_fwd2(cur, oth, tw2t, xa, j, K, H);
-      __syncthreads();
-#pragma unroll
-      for (int h = 0; h < 2; h++) {
-        v2f zb[8];
-        xf_fwd3<true>(oth, zb, h, w3r[h], t3a, t3b, t3c, j, K, H);
-#pragma unroll
-        for (int t = 0; t < 8; t++) acc[h][t] = pk_cfmac(zb[t], za[h][t], acc[h][t]);   // + conj(A_s[k]) B_s[k]
-      }
-    }
-    // ---- inverse 8 x 16 x 16 of the group's cross-spectrum (registers -> cur -> oth -> registers): cur was last read by a
-    // pass 2, oth by the pass 3 in front of the barrier below
-#pragma unroll
-    for (int h = 0; h < 2; h++) xf_invA(cur, acc[h], j + T * h, H);
-    __syncthreads();
-    xf_invB(cur, oth, twBt, xa, j, K, H);
-    __syncthreads();
-    v2f y[16];
-    const v2f none[16] = {};                               // (the resident twiddles xf_invC<false> does not look at)
-    xf_invC<false>(oth, y, xa, none, t3a, t3b, t3c, K, H);
-    float* __restrict__ dst = p.part + unit * (uint64_t)lags;
-#pragma unroll
-    for (int t = 0; t < 9; t++) {
-      const int k = j + T * t;                               // lag k - L
-      if (k < lags) dst[k] = y[t].x * 0x1p-11f;
-    }
-    // (the next unit's pass 1 writes cur, which pass B has read in front of the last barrier; its pass 2 writes oth behind
-    // a barrier that pass C lies in front of)
+      });
+    corr_finish(c, acc, p.part + unit * (uint64_t)lags, lags);
     if (!more) break;
     unit = next;
     u = unit_of(p, pairs, next);
@@ -250,8 +131,7 @@ __global__ __launch_bounds__(CREST_THREADS) void track_crest_kernel(const Params
       if (p.from_corr) {
         sum = crow[k];
       } else {
-        sum = 0.0;
-        for (uint32_t s = 0; s < p.n_groups; ++s) sum += (double)src[(uint64_t)s * lags + k];
+        sum = corr_unit_sum(src + k, p.n_groups, (uint64_t)lags);
         if (crow) crow[k] = sum;
       }
       r[k] = sum;
