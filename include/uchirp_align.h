@@ -54,6 +54,7 @@
  * delays over time; per-microphone clock offsets (an array shares one clock); adaptive weights; capture into a graph;
  * resolving whole-cycle ambiguity at low SNR beyond reporting runner_up (at -12 dB about half of the pairs land whole
  * carrier cycles off; delay-and-sum beams of eight microphones steered that way still decoded).
+ * Weights on the chirps' band, which keep the crest on its cycle at low SNR: uchirp_wcorr.h.
  */
 #ifndef UCHIRP_ALIGN_H
 #define UCHIRP_ALIGN_H

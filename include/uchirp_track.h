@@ -54,7 +54,8 @@
  * rounding error of them.
  *
  * OUT OF SCOPE: fitting lines to the delays on the GPU; PHAT or other spectral weightings; lag ranges beyond
- * UC_TRACK_MAX_LAG; capture into a graph; resolving whole-cycle ambiguity at low SNR beyond reporting runner_up.
+ * UC_TRACK_MAX_LAG; capture into a graph; resolving whole-cycle ambiguity at low SNR beyond reporting runner_up.  Fixed
+ * spectral weights (the chirps' band), which keep the crest on its cycle at low SNR: uchirp_wcorr.h.
  */
 #ifndef UCHIRP_TRACK_H
 #define UCHIRP_TRACK_H

@@ -51,7 +51,8 @@
  *   the estimate is the candidate of greatest height, the first one on a tie.
  *
  * OUT OF SCOPE: PHAT or other spectral weightings; lag ranges beyond UC_XCORR_MAX_LAG; tracking delays over time; capture
- * into a graph; resolving whole-cycle ambiguity at low SNR beyond reporting runner_up.
+ * into a graph; resolving whole-cycle ambiguity at low SNR beyond reporting runner_up.  Fixed spectral weights (the chirps'
+ * band), which keep the crest on its cycle at low SNR: uchirp_wcorr.h.
  */
 #ifndef UCHIRP_XCORR_H
 #define UCHIRP_XCORR_H

@@ -205,6 +205,51 @@ __device__ __forceinline__ void corr_finish(const CorrCtx& c, const v2f (&acc)[2
   // a barrier that pass C lies in front of)
 }
 
+// ---- the weighted unit (wcorr_kernel, uc_wcorr_kernel.hip; include/uchirp_wcorr.h): a real, even weight per bin on the
+// group's cross-spectrum, between the last corr_segment and the finish, and a finish that stores a part of the outputs
+
+constexpr int kCorrWeightBins = kN / 2 + 1;   // the staged table: w[k], k = 0 .. 1024
+
+// thread j's sixteen weights: wv[t] = (W[j + 256 t], W[j + 128 + 256 t]), W[k] = w[k] for k <= 1024, w[2048 - k] above.
+// table: kCorrWeightBins floats; every index read lies inside it, and the load goes through the range check anyway
+__device__ __forceinline__ void corr_load_weights(const float* table, int j, v2f (&wv)[8]) {
+  const __amdgpu_buffer_rsrc_t rw = make_rsrc(table, kCorrWeightBins * 4);
+#pragma unroll
+  for (int t = 0; t < 8; t++) {
+    const int k0 = j + 2 * kXfThreads * t, k1 = k0 + kXfThreads;
+    wv[t] = mkv(buf_ld32(rw, (k0 <= kN / 2 ? k0 : kN - k0) * 4, 0), buf_ld32(rw, (k1 <= kN / 2 ? k1 : kN - k1) * 4, 0));
+  }
+}
+
+// acc[h][t] *= W[j + 128 h + 256 t]: one multiply for the real part and one for the imaginary part (one packed instruction)
+__device__ __forceinline__ void corr_weight(v2f (&acc)[2][8], const v2f (&wv)[8]) {
+#pragma unroll
+  for (int t = 0; t < 8; t++) {
+    acc[0][t] = pk_scale_lo(acc[0][t], wv[t]);
+    acc[1][t] = pk_scale_hi(acc[1][t], wv[t]);
+  }
+}
+
+// the end of a weighted unit: dst[k] = output k0 + k of the inverse transform, k < lags; k0 + lags <= 1025.  What
+// corr_finish does, with the window of stored outputs moved by k0 (corr_finish is this at k0 = 0; it is kept as it is so
+// that the kernels built on it keep their bytes)
+__device__ __forceinline__ void corr_finish_at(const CorrCtx& c, const v2f (&acc)[2][8], float* __restrict__ dst, int k0, int lags) {
+  __builtin_assume((unsigned)c.j < (unsigned)kXfThreads);
+#pragma unroll
+  for (int h = 0; h < 2; h++) xf_invA(c.cur, acc[h], c.j + kXfThreads * h, c.H);
+  __syncthreads();
+  xf_invB(c.cur, c.oth, c.twBt, c.xa, c.j, c.K, c.H);
+  __syncthreads();
+  v2f y[16];
+  const v2f none[16] = {};
+  xf_invC<false>(c.oth, y, c.xa, none, c.t3a, c.t3b, c.t3c, c.K, c.H);
+#pragma unroll
+  for (int t = 0; t < 9; t++) {
+    const int k = c.j + kXfThreads * t - k0;             // output j + 128 t, up to index 1024 at t = 8
+    if ((unsigned)k < (unsigned)lags) dst[k] = y[t].x * 0x1p-11f;
+  }
+}
+
 // one lag's sum over a window's units: src[s * lags], s < n_groups, added in double in ascending group order
 __device__ __forceinline__ double corr_unit_sum(const float* src, uint32_t n_groups, uint64_t lags) {
   double sum = 0.0;
