@@ -40,6 +40,9 @@ NAN_WORD = {"float32": np.float32(np.nan), "int32": np.int32(-2 ** 31)}     # wh
 
 SWEEP_CASES = ["rx_real-literal", "rx_real-matched", "sync_cplx-literal", "sync_cplx-matched",
                "rx_real-wide294", "rx_real-wide318", "sync_cplx-wide294", "sync_cplx-wide318"]
+# ... and the widths at which the owner of bin bandwidth2 changes (tone_sweep_util.SEAM_WIDTHS): wave 1 slot 0, wave 1 slot 1,
+# the first WIDE window, the first bin of the third round
+SWEEP_CASES += [tsu.seam_name(kind, w) for w in (64, 128, 192, 256) for kind in ("rx_real", "sync_cplx")]
 DTYPES = ["float32", "int32"]
 
 

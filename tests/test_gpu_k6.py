@@ -25,6 +25,7 @@ import pytest
 from uchirp import synth
 from oracle import uco
 from parity_util import MAG_TOL, check_history, clear_symbols
+import tone_sweep_util as tsu
 
 pytestmark = pytest.mark.gpu
 
@@ -193,6 +194,43 @@ def test_window_spectrum_matches_the_oracle_bin_by_bin(uchirp, name, kw):
     torch.cuda.synchronize()
     gh = e.window_spectrum(frames.reshape(-1)[: 2048 * 9], stride=256)
     assert gd.shape[0] == 65 and np.array_equal(gd.cpu().numpy().view(np.uint32), gh.view(np.uint32))
+
+
+SPEC_SEAMS = [tsu.seam_name(kind, w) for kind, widths in (("rx_real", (2, 64, 128, 190, 192, 256)), ("sync_cplx", (2, 64, 128, 190, 192, 256)),
+                                                          ("dechirp_down", (8, 64, 128, 192, 256))) for w in widths]
+
+
+@pytest.mark.parametrize("case", SPEC_SEAMS)
+def test_window_spectrum_of_the_tone_sweeps_at_the_seam_widths(uchirp, case):
+    """The SPEC build at the widths where bin bandwidth2 changes its owner (tests/tone_sweep_util.py: SEAM_WIDTHS), on the
+    float32 tone sweep of the case -- every window bin holds the peak in some frame: every stored bin against the oracle's
+    spectrum, and the statistics of uc_process_batch the maxima of exactly the stored values."""
+    variant, cfg = tsu.config(case)
+    o, buf, n_frames, _, _, _ = tsu.batch(case)
+    frames = buf.reshape(n_frames, N)
+    e = uchirp.Engine(variant, mag_mean=1000.0, **cfg)
+    bw2 = tsu.CASES[case][3]["bw2"]
+    assert e.bandwidth2 == o.bandwidth2 == bw2
+    g = e.window_spectrum(frames)
+    assert g.shape == (n_frames, e.spf, 2 * bw2 + 1)
+    _, st = e.process(frames)
+    worst, off, unequal = 0.0, [], []
+    for f in range(n_frames):
+        ref = o.spectrum(frames[f])                        # [spf, n] float64
+        for h in range(e.spf):
+            want = np.concatenate([ref[h][N - bw2:], ref[h][:bw2 + 1]])
+            worst = max(worst, float(np.abs(g[f, h] - want).max() / (MAG_TOL * want.max())))
+            if not np.abs(g[f, h] - want).max() <= MAG_TOL * want.max():
+                off.append((f, h))
+            mr, ml = g[f, h, bw2:2 * bw2].max(), g[f, h, :bw2].max()
+            if not (st[f, h]["mag_max_right"] == mr and st[f, h]["mag_max_left"] == ml):
+                unequal.append((f, h))
+    print("SPEC %-22s %5d frames x %d histories x %3d bins  worst |gpu - oracle| / (MAG_TOL x window max) %.3f, spectra off the bar "
+          "%d, statistics that are not the maxima of the stored values bit for bit %d"
+          % (case, n_frames, e.spf, 2 * bw2 + 1, worst, len(off), len(unequal)))
+    assert not off, "first (frame, history): %r" % off[:8]
+    assert not unequal, "first (frame, history): %r" % unequal[:8]
+    e.close()
 
 
 @pytest.mark.parametrize("name", ["rx_real", "sync_cplx", "dechirp_down"])

@@ -22,6 +22,10 @@ Per case, float32 samples and int32 DFSDM words:
      the bit comparison, and a permutation of the frames -- other partners -- goes through 1 - 3 again;
   5. the same batch under UC_GRID=1 with groups of 2 (one workgroup walks every ring slot): the same bits.
 
+The band kernel is swept at the seams of its window search too (tone_sweep_util.SEAM_WIDTHS: the widths at which bin bandwidth2
+changes its owner), float32 at every width and int32 where the owner changes; test_edge_frames_at_the_seams adds the all-zero
+and all-NaN frames there, whose answer is the edge-bin owner's alone.
+
 The parametrize ids name the kernel instantiation a case reaches (csrc/uc_band_kernel.hip: UC_DISPATCH,
 csrc/uc_iq_kernel.hip: UC_IQ_DISPATCH); the geometry that selects it is asserted.  `pytest -s` prints the figures."""
 import numpy as np
@@ -69,6 +73,16 @@ BUILDS = [
     ("iq1024<BB1,FIRM1>", "iq1024-bb1", MFMA, None),
     ("iq1024<BB1,FIRM1>-narrow", "iq1024-bb2", MFMA, None),     # with the flag set the narrow geometry goes to <.., 1, 1> too
 ]
+# band kernel at the seams of its window search (tone_sweep_util.SEAM_WIDTHS): the widths at which bin bandwidth2 changes its
+# owner, wave 1 loses its common bins, the third round of the WIDE build gets its first bin
+_DEFAULT = {"rx_real": "band<RxReal,W3>-w%d", "sync_cplx": "band<Cplx,W2>-w%d", "dechirp_down": "band<Pair,W3>-w%d"}
+_WIDE = {"rx_real": "band<RxReal,W2,WIDE>-%d", "sync_cplx": "band<Cplx,W2,WIDE>-%d", "dechirp_down": "band<Pair,W2,WIDE>-%d"}
+SEAM_BUILDS = [((_WIDE if w > 191 else _DEFAULT)[kind] % w, tsu.seam_name(kind, w), {}, None)
+               for kind, widths in tsu.SEAM_WIDTHS.items() for w in widths]
+BUILDS += SEAM_BUILDS
+SEAM_INT32 = (64, 128, 192, 256)        # the word type changes the load alone: int32 where the owner of bin bandwidth2 changes
+SWEEPS = [pytest.param(*b, dtype, id="%s-%s" % (b[0], dtype)) for b in BUILDS for dtype in ("float32", "int32")
+          if dtype == "float32" or b not in SEAM_BUILDS or tsu.CASES[b[1]][3]["bw2"] in SEAM_INT32]
 
 
 @pytest.fixture(scope="module")
@@ -147,8 +161,7 @@ def _against_the_oracle(sw, gs, gst, label):
         assert (gs == 0xFF).all()
 
 
-@pytest.mark.parametrize("dtype", ["float32", "int32"])
-@pytest.mark.parametrize("build,name,env,stride", BUILDS, ids=[b[0] for b in BUILDS])
+@pytest.mark.parametrize("build,name,env,stride,dtype", SWEEPS)
 def test_tone_sweep(uchirp, monkeypatch, uc_tuning, build, name, env, stride, dtype):
     sw, _ = tsu.sweep(name, dtype, stride)
     o = sw.o
@@ -177,6 +190,63 @@ def test_tone_sweep(uchirp, monkeypatch, uc_tuning, build, name, env, stride, dt
     assert np.array_equal(tst.view(np.uint32), gst.view(np.uint32)), label
     e.close()
     e1.close()
+
+
+def _loudest_left_edge(sw):
+    """The frame of a sweep whose tone is the clear winner on the left window's FIRST element (bin bandwidth2) and largest there."""
+    edge = sw.windows["left"][0]
+    on = [f for f in range(sw.n_frames) for h in range(sw.o.spf) if sw.clear["left"][h, f] and sw.win["left"][h, f] == edge]
+    assert on
+    return max(on, key=lambda f: float(sw.records[f]["mag_max_left"].max()))
+
+
+@pytest.mark.parametrize("env", [{}, {"UC_GRID": "1", "UC_BAND_GROUP": "2"}], ids=["default", "grid1-group2"])
+@pytest.mark.parametrize("build,name", [(b[0], b[1]) for b in SEAM_BUILDS], ids=[b[0] for b in SEAM_BUILDS])
+def test_edge_frames_at_the_seams(uchirp, monkeypatch, uc_tuning, build, name, env):
+    """All-zero and all-NaN frames at every seam width, by the rule of test_gpu_wide.py::test_wide_edge_frames_and_peaks_in_every_
+    round: magnitudes and snr equal to the oracle's or both NaN, the three indices and the symbol equal.  In a zero frame every
+    bin ties and arm_max_f32 keeps the FIRST element of each window: bin 0 on the right, bin bandwidth2 on the left -- the answer
+    of the one thread that owns that bin, whichever wave and slot the width puts it in.
+
+    Frames 0, 1 zero, 2 NaN, 3 zero, 4 noise, 5 zero; behind them the sweep's loudest tone on bin bandwidth2, a zero frame, and
+    one more zero frame: with groups of 2 the ring slots alternate, so that this last one sits in the slot the loud frame wrote
+    last.  DECHIRP_DOWN transforms frames (2u, 2u + 1) together: the loud frame, the zero frame and the one more are pairs of
+    their own there, and only zero frames whose partner is zero are compared."""
+    sw, _ = tsu.sweep(name)
+    o, n = sw.o, sw.o.n
+    paired = tsu.CASES[name][0] == "dechirp_down"
+    loud = sw.frame(_loudest_left_edge(sw)).astype(np.float32)
+    zero = np.zeros(n, np.float32)
+    x = [zero, zero, np.full(n, np.nan, np.float32), zero,
+         (1000.0 * np.random.default_rng(1).standard_normal(n)).astype(np.float32), zero]
+    if paired:
+        x += [loud, loud, zero, zero, zero, zero]
+        check = (0, 1, 8, 9, 10, 11)
+    else:
+        x += [loud, zero, zero]
+        check = (0, 1, 2, 3, 5, 7, 8)
+    x = np.stack(x)
+    e = _engine(uchirp, monkeypatch, name, "float32", env)
+    _assert_geometry(e, o, name, {}, None)
+    rs, rst = o.process(x)
+    gs, gst = e.process(x)
+    loud_at = 6
+    assert rst[loud_at]["mag_max_left"].max() > 1e4      # what a stale edge word would hold
+    for f in check:
+        for h in range(o.spf):
+            if not np.isnan(x[f]).any():                 # the oracle's answer is the first element of each window
+                assert rst[f, h]["mag_max"] == 0.0 and rst[f, h]["max_freq_right"] == sw.record_of_bin("right", 0)
+                assert rst[f, h]["max_freq_left"] == sw.record_of_bin("left", sw.windows["left"][0])
+            for fld in ("mag_max", "mag_max_left", "mag_max_right", "snr"):
+                a, b = float(gst[f, h][fld]), float(rst[f, h][fld])
+                assert (np.isnan(a) and np.isnan(b)) or a == b, (build, f, h, fld, a, b)
+            for fld in ("max_freq", "max_freq_left", "max_freq_right"):
+                assert gst[f, h][fld] == rst[f, h][fld], (build, f, h, fld, int(gst[f, h][fld]), int(rst[f, h][fld]))
+        assert gs[f] == rs[f], (build, f)
+    print("%-32s %-12s %d frames: %d zero / NaN frames x %d histories equal the oracle's in 7 fields and the symbol; the loud frame's "
+          "left edge %.4g" % (build, "+".join("%s=%s" % kv for kv in env.items()) or "default", len(x), len(check), o.spf,
+                              float(rst[loud_at]["mag_max_left"].max())))
+    e.close()
 
 
 @pytest.mark.parametrize("dtype", ["float32", "int32"])

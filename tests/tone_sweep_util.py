@@ -59,6 +59,35 @@ CASES = {
     "iq2048-bb0": ("iq", dict(_FW, n=2048), "iq_fw", dict(bw2=60)),
 }
 
+# The seams of the band kernel's window search (csrc/uc_band_kernel.hip): the widths at which bin bandwidth2 -- the left window's
+# first element -- changes its owner.  Default build: thread j owns bin j, wave 1 also bin 128 + lane; bin bandwidth2 belongs to
+# wave 0 below 64, to wave 1 from 64 (slot 0) and from 128 (slot 1, lane 0 first); wave 1 has no common bins up to 64 and no
+# slot-1 bins up to 128.  WIDE build (from 192): the third round, 256 + lane on wave 1, has its first bin at 256.
+SEAM_WIDTHS = {
+    "rx_real": (2, 62, 64, 66, 126, 128, 130, 190, 192, 254, 256, 258),
+    "sync_cplx": (2, 62, 64, 66, 126, 128, 130, 190, 192, 254, 256, 258),
+    "dechirp_down": (8, 56, 64, 72, 120, 128, 136, 184, 192, 248, 256, 264),
+}
+
+
+def _band(b, fs, f0):
+    """The band that gives `bandwidth` b: (f1 - f0) n / fs = b + 0.5 -- the half bin keeps the float32 truncation of
+    build_tables away from an integer."""
+    return dict(f0=f0, f1=f0 + (b + 0.5) * fs / 2048)
+
+
+def seam_name(kind, bw2):
+    return "%s-%s%d" % (kind, "wide" if bw2 > 191 else "w", bw2)
+
+
+for _kind, _widths in SEAM_WIDTHS.items():
+    for _w in _widths:
+        if _kind == "dechirp_down":       # bandwidth2 = 8 x bandwidth
+            CASES[seam_name(_kind, _w)] = (_kind, dict(fs=100000.0, **_band(_w // 8, 100000.0, 17000.0)), "ref_tone", dict(bw2=_w))
+        else:                             # bandwidth2 = 2 x bandwidth, at the default 78 125 Hz and time_frame
+            CASES[seam_name(_kind, _w)] = (_kind, _band(_w // 2, 78125.0, 14000.0), "chirp", dict(bw2=_w))
+SEAM_CASES = [seam_name(k, w) for k, ws in SEAM_WIDTHS.items() for w in ws]
+
 
 def config(name):
     """(variant, keyword arguments of Oracle / Engine) of a case; mag_mean is the caller's."""
