@@ -22,6 +22,20 @@
  * so a buffer does not depend on the launch geometry nor on how a recording is cut into calls (first_sample).
  * The device evaluates the phase in turns in double precision, reduces it and takes ONE float sine per sample
  * (cos a + sin a = sqrt 2 sin(a + pi / 4)): within 8 ulp of float at the peak amplitude * sqrt 2 of the definition above.
+ *
+ * Reach.  The definition is meant in exact arithmetic on the arguments' binary values (1e-6 is the number 10^-6), and the
+ * bound holds at every position the calls accept: first_sample <= 2^52 (UC_LINK_MAX_FIRST_SAMPLE), n_samples <= 2^40
+ * (UC_LINK_MAX_SAMPLES), any finite lead_samples, |ppm| <= 200; a call beyond them is refused with -EINVAL.  tt is not
+ * computed as the difference of two times of the size of j / fs_out, whose error would grow with j (about 10 ulp at
+ * j = 2^33, 30 hours at 78 125 Hz), but from an integer distance (uc_link_frame_origin):
+ *
+ *            origin = the integer nearest to lead_samples / (1 + ppm * 1e-6)      (where the frame begins)
+ *            t0     = (origin * (1 + ppm * 1e-6) - lead_samples) / fs_out          (under one sample; summed exactly)
+ *            tt     = (j - origin) * ((1 + ppm * 1e-6) / fs_out) + t0
+ *
+ * Shift.  With ppm = 0 the signal is a function of j - lead_samples alone: adding one integer S to lead_samples and to
+ * first_sample, where lead_samples + S is a double and first_sample + S <= 2^52, changes no bit of the signal.  (The noise
+ * belongs to the absolute sample index and moves with it.)
  */
 #ifndef UCHIRP_LINK_H
 #define UCHIRP_LINK_H
@@ -33,7 +47,7 @@
 extern "C" {
 #endif
 
-#define UC_LINK_ABI_VERSION 1
+#define UC_LINK_ABI_VERSION 2 /* 2: uc_link_frame_origin; the reach and the shift property are part of the contract */
 
 /* output formats.  I32 and F32 carry the values of UC_DTYPE_I32 / UC_DTYPE_F32 of uchirp.h. */
 #define UC_LINK_DTYPE_I32 0 /* DFSDM words: round-to-nearest-even(x) * 256, the 24-bit sample in bits 31:8 (saturating) */
@@ -41,6 +55,9 @@ extern "C" {
 #define UC_LINK_DTYPE_I16 3 /* int16, truncated toward zero (what a WAV writer's cast does), saturating */
 
 #define UC_LINK_MAX_TEXT 4096 /* largest text_stride */
+
+#define UC_LINK_MAX_FIRST_SAMPLE (1ull << 52) /* largest first_sample */
+#define UC_LINK_MAX_SAMPLES (1ull << 40)      /* largest n_samples */
 
 typedef struct uc_link uc_link;
 
@@ -60,11 +77,22 @@ typedef struct uc_link_stream {
   uint32_t text_len;   /* bytes of this stream's text (<= text_stride) */
 } uc_link_stream;
 
+/* what the host derives from one stream's lead_samples, ppm and fs_out (24 bytes) */
+typedef struct uc_link_origin {
+  int64_t origin; /* the integer nearest to lead_samples / (1 + ppm * 1e-6), ties to even; held to +-2^53 */
+  double t0;      /* (origin * (1 + ppm * 1e-6) - lead_samples) / fs_out: seconds since the frame began at sample origin */
+  double rate;    /* (1 / fs_out) * (1 + ppm * 1e-6) in double: seconds of transmitter time per output sample */
+} uc_link_origin;
+
 int uc_link_abi_version(void);
 /* text of the calling thread's last error ("" if none) */
 const char* uc_link_last_error(void);
 /* the format of the reference transmission: 44100 Hz, 0.0262 s, 16000 .. 19000 Hz, 7 preamble symbols, 12 guard symbols */
 int uc_link_default_config(uc_link_config* cfg);
+/* The three numbers the kernels take a stream's time from (see "Reach"); pure host arithmetic, needs no GPU.  t0 is within
+ * 2 ulp of its rational value for |ppm| <= 200 and |lead_samples| <= 2^53.  -EINVAL: out is NULL; lead_samples or ppm not
+ * finite; fs_out not positive and finite. */
+int uc_link_frame_origin(double lead_samples, float ppm, double fs_out, uc_link_origin* out);
 /* -ENODEV ("no CPU path") when no GPU is visible; -EINVAL for a config that is not a frame format */
 int uc_link_create(int device, const uc_link_config* cfg, uc_link** out);
 void uc_link_destroy(uc_link* link);

@@ -25,6 +25,13 @@
  * sigma and seed; and a value depends on (seed, m, j, the microphone's paths, their texts) only, never on the launch
  * geometry nor on how a recording is cut into calls (first_sample).  Each path is within 8 float ulp of its own peak
  * |gain| * sqrt 2 of the definition; each addition rounds once.
+ *
+ * Reach and shift are uchirp_link.h's: the bound holds at every position uc_scene_render accepts (first_sample <= 2^52 =
+ * UC_LINK_MAX_FIRST_SAMPLE, n_samples <= 2^40 = UC_LINK_MAX_SAMPLES, any finite lead_samples, |ppm| <= 200; beyond them
+ * -EINVAL), because every path's time comes from the integer distance of the sample to the path's own origin
+ * (uc_link_frame_origin of uchirp_link.h states the three numbers; this library derives them with the same code).  A scene
+ * whose paths all have ppm = 0 is a function of j - lead_samples per path: one integer S added to every lead_samples and
+ * to first_sample, where each sum is a double and first_sample + S <= 2^52, changes no bit of the signal terms.
  */
 #ifndef UCHIRP_SCENE_H
 #define UCHIRP_SCENE_H

@@ -302,7 +302,7 @@ def test_plain_c_host_transmits_hello_world(link, tmp_path):
     out = subprocess.run([exe, "8"], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stdout + out.stderr
     lines = out.stdout.splitlines()
-    assert lines[0] == "uc_link_abi_version 1 (header 1)"
+    assert lines[0] == "uc_link_abi_version 2 (header 2)"
     got = [int(v) for v in lines[1].split()[1:]]
     want = tx.tone_int16()[1155:1155 + 8]
     assert list(want[:3]) == [-19999, 28207, -16859]

@@ -5,10 +5,12 @@
 
 namespace uc_link_dev {
 
-// one stream as the kernel reads it (32 bytes)
+// one stream as the kernel reads it (40 bytes).  rate, t0 and origin are frame_origin()'s (uc_link_host.hpp): the seconds
+// since the frame began at absolute sample j are (j - origin) * rate + t0, an integer difference and a time under a sample
 struct Stream {
   double rate;        // seconds of transmitter time per output sample: (1 / fs_out) * (1 + ppm * 1e-6)
-  double lead_s;      // lead_samples / fs_out
+  double t0;          // (origin * (1 + ppm * 1e-6) - lead_samples) / fs_out: the frame's time at sample `origin`
+  int64_t origin;     // the sample nearest to where the frame begins on the receiver's clock
   float amp;          // amplitude * sqrt 2
   float sigma;
   uint32_t text_len;

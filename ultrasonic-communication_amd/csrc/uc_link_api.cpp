@@ -28,6 +28,17 @@ int uc_link_default_config(uc_link_config* cfg) {
   return 0;
 }
 
+int uc_link_frame_origin(double lead_samples, float ppm, double fs_out, uc_link_origin* out) {
+  if (!out) return fail(-EINVAL, "uc_link_frame_origin: out is NULL");
+  if (!std::isfinite(lead_samples) || !std::isfinite(ppm)) return fail(-EINVAL, "uc_link_frame_origin: lead_samples and ppm must be finite");
+  if (!(fs_out > 0.0) || !std::isfinite(fs_out)) return fail(-EINVAL, "uc_link_frame_origin: fs_out must be positive");
+  const FrameOrigin fo = frame_origin(lead_samples, ppm, fs_out);
+  out->origin = fo.origin;
+  out->t0 = fo.t0;
+  out->rate = fo.rate;
+  return 0;
+}
+
 int uc_link_create(int device, const uc_link_config* cfg, uc_link** out) {
   if (!out) return fail(-EINVAL, "uc_link_create: out is NULL");
   *out = nullptr;
@@ -67,7 +78,9 @@ int uc_link_transmit(uc_link* l, const uint8_t* text, size_t text_stride, const 
   if (text_stride > UC_LINK_MAX_TEXT) return fail(-EINVAL, "uc_link_transmit: text_stride %zu > %d", text_stride, UC_LINK_MAX_TEXT);
   const size_t stride = stride_or(stride_elems, n_samples);
   if (int rc = check_stride(WHO, "stride_elems", stride_elems, "n_samples", n_samples)) return rc;
-  if (first_sample > (1ull << 52) || n_samples > (1ull << 40)) return fail(-EINVAL, "uc_link_transmit: sample range too large");
+  // the reach: every sample index stays below 2^53, so its distance to a stream's origin is exact in double (frame_time())
+  if (first_sample > UC_LINK_MAX_FIRST_SAMPLE || n_samples > UC_LINK_MAX_SAMPLES)
+    return fail(-EINVAL, "uc_link_transmit: sample range too large (first_sample <= 2^52, n_samples <= 2^40)");
   bool any_text = false;
   for (size_t s = 0; s < n_streams; ++s) {
     const uc_link_stream& q = params[s];
@@ -93,8 +106,10 @@ int uc_link_transmit(uc_link* l, const uint8_t* text, size_t text_stride, const 
   Stream* rec = (Stream*)sl->pinned;
   for (size_t s = 0; s < n_streams; ++s) {
     const uc_link_stream& q = params[s];
-    rec[s].rate = (1.0 / fs_out) * (1.0 + (double)q.ppm * 1e-6);
-    rec[s].lead_s = q.lead_samples / fs_out;
+    const FrameOrigin fo = frame_origin(q.lead_samples, q.ppm, fs_out);
+    rec[s].rate = fo.rate;
+    rec[s].t0 = fo.t0;
+    rec[s].origin = fo.origin;
     rec[s].amp = (float)((double)q.amplitude * 1.4142135623730951);
     rec[s].sigma = q.sigma;
     rec[s].text_len = q.text_len;

@@ -51,23 +51,40 @@ __device__ __forceinline__ void box_muller(uint32_t wa, uint32_t wb, float& z0, 
   z1 = r * (neg_both ? -s : s);
 }
 
-// seconds since the frame began at absolute sample jd, and the (unclamped) index of the frame's symbol at that time.
-// ST: a record with rate, lead_s and amp (Stream; the scene's Path).  Both are monotone in jd, rounding included, which
-// is what lets the scene kernel decide from a tile's first and last sample that a path is silent over all of it.
-// Every caller must take its times from these two functions and from nothing else: they are force-inlined under one
-// contraction setting, so every site gets the same roundings (today one double fma and one add-then-multiply).  An
-// explicit fma() here would say so in the source, but it changes the link kernels' machine code, which is pinned.
+// seconds since the frame began at absolute sample j = j0 + i (j0 the first sample of j's quad, a multiple of 4; i = 0 .. 3),
+// and the (unclamped) index of the frame's symbol at that time.  ST: a record with rate, t0, origin and amp (Stream; the
+// scene's Path).
+// The time is taken from the INTEGER distance to the stream's origin, the sample nearest to the frame's beginning
+// (frame_origin() of uc_link_host.hpp): j0 - origin is exact in int64, its double and the sum with i are exact while the
+// distance is below 2^53 - 3, and t0 is under a sample, so the one rounding of the fma is 2^-53 of a time inside the frame
+// wherever in a recording the frame lies.  (The form j * rate - lead_s that stood here cancelled two times of size j / fs_out:
+// 10 ulp of the signal at j = 2^33, 800 at 2^40.)  The conversion is taken once per quad (quad_distance) because an int64 ->
+// double conversion costs several double-precision instructions and a lane owns the quad's four samples; the quad belongs to
+// the absolute sample grid, not to the call, so the time stays a function of j alone.
+// Both functions are monotone in j, rounding included, which is what lets the scene kernel decide from a tile's first
+// and last sample that a path is silent over all of it.  The steps: a = j0 - origin is exact (j < 2^53, |origin| <= 2^53, so
+// |a| < 2^54); D(j) = RN(RN(a) + i) is monotone inside a quad (RN is) and from a quad's last sample to the next quad's first:
+// |a| < 2^54 leaves RN(a) <= a + 1, so RN(a) + 3 <= a + 4 and RN(RN(a) + 3) <= RN(a + 4); d -> d * rate + t0 is monotone
+// in exact arithmetic (either way, by the sign of rate) and the fma rounds it once; symbol_at adds a constant, multiplies by
+// a positive constant and takes the floor.
+// Every caller must take its times from these functions and from nothing else (the tile's last sample as its quad's
+// i = 3): the fma is written out, so every site gets the same roundings whatever the contraction setting.
 template <class ST>
-__device__ __forceinline__ double frame_time(const ST& st, double jd) {
-  return jd * st.rate - st.lead_s;
+__device__ __forceinline__ double quad_distance(const ST& st, uint64_t j0) {
+  return (double)((int64_t)j0 - st.origin);
+}
+template <class ST>
+__device__ __forceinline__ double frame_time(const ST& st, double d0, int i) {
+  return fma(d0 + (double)i, st.rate, st.t0);
 }
 __device__ __forceinline__ double symbol_at(const Params& p, double tt) { return floor((tt + 1e-10) * p.inv_sym_dur); }
 
-// the transmitter's law at absolute sample jd of one stream (0 in silence and outside the frame)
+// the transmitter's law at sample i of the quad whose first sample lies d0 = quad_distance() from the stream's origin
+// (0 in silence and outside the frame)
 template <class ST>
 __device__ __forceinline__ float signal_at(const Params& p, const ST& st, const uint8_t* __restrict__ text, uint32_t n_on,
-                                           double jd) {
-  const double tt = frame_time(st, jd);
+                                           double d0, int i) {
+  const double tt = frame_time(st, d0, i);
   const double q = symbol_at(p, tt);
   // symbols 1 .. n_on - 1 sound (0 is the leading G; from n_on on: the guard, then nothing)
   if (!(q >= 1.0 && q < (double)n_on)) return 0.0f;

@@ -8,6 +8,8 @@
 // barrier, no atomics.  A value depends only on (seed, stream, sample index, the stream's parameters), never on the
 // grid or on where a call's first_sample cuts the recording.
 //
+// Time: the seconds since a stream's frame began come from the integer distance of the sample to the stream's origin
+// (frame_time() of uc_link_dev.hpp), so their error does not grow with the position in the recording.
 // Signal: the phase f t - 1/4 (+ 1/8: cos a + sin a = sqrt 2 sin(a + pi/4)) is kept in TURNS in double precision (up
 // to ~500 turns inside a symbol: float would leave 3e-5 turns), reduced to [-1/2, 1/2] and only then rounded to float;
 // sinpif takes it from there.  sinpif is the library function, not the hardware sine: the bound of 8 float ulp at the
@@ -42,9 +44,9 @@ __global__ __launch_bounds__(THREADS) void link_kernel(const Params p, const Str
     const uint8_t* __restrict__ tx = text + (size_t)s * p.text_stride;
     const uint32_t n_on = 2u + p.n_preamble + 8u * st.text_len;
     float v[4];
-    const double jd = (double)j0;
+    const double d0 = quad_distance(st, j0);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = signal_at(p, st, tx, n_on, jd + (double)i);
+    for (int i = 0; i < 4; ++i) v[i] = signal_at(p, st, tx, n_on, d0, i);
     if (st.sigma != 0.0f) {
       const Words w = philox4x32_10((uint32_t)quad, (uint32_t)(quad >> 32), s, 0u, (uint32_t)p.seed, (uint32_t)(p.seed >> 32));
       float z[4];

@@ -10,11 +10,12 @@ using uc_link_dev::Params;
 using uc_link_dev::THREADS;
 using uc_link_dev::TILE_QUADS;
 
-// one path as the kernel reads it (32 bytes): what uc_link_dev::Stream holds for a stream, the sounding symbols of its
+// one path as the kernel reads it (40 bytes): what uc_link_dev::Stream holds for a stream, the sounding symbols of its
 // transmission (2 + n_preamble + 8 * text_len) and where its text lies
 struct Path {
   double rate;        // seconds of transmitter time per output sample: (1 / fs_out) * (1 + ppm * 1e-6)
-  double lead_s;      // lead_samples / fs_out
+  double t0;          // (origin * (1 + ppm * 1e-6) - lead_samples) / fs_out
+  int64_t origin;     // the sample nearest to where the frame begins on the receiver's clock
   float amp;          // gain * sqrt 2
   uint32_t n_on;
   uint32_t tx;

@@ -71,7 +71,9 @@ int uc_scene_render(uc_scene* l, const uint8_t* text, size_t text_stride, const 
   if (text_stride > UC_LINK_MAX_TEXT) return fail(-EINVAL, "uc_scene_render: text_stride %zu > %d", text_stride, UC_LINK_MAX_TEXT);
   const size_t stride = stride_or(stride_elems, n_samples);
   if (int rc = check_stride(WHO, "stride_elems", stride_elems, "n_samples", n_samples)) return rc;
-  if (first_sample > (1ull << 52) || n_samples > (1ull << 40)) return fail(-EINVAL, "uc_scene_render: sample range too large");
+  // the reach: every sample index stays below 2^53, so its distance to a path's origin is exact in double (frame_time())
+  if (first_sample > UC_LINK_MAX_FIRST_SAMPLE || n_samples > UC_LINK_MAX_SAMPLES)
+    return fail(-EINVAL, "uc_scene_render: sample range too large (first_sample <= 2^52, n_samples <= 2^40)");
   bool any_text = false;
   for (size_t t = 0; t < n_tx; ++t) {
     if (text_len[t] > text_stride)
@@ -110,8 +112,10 @@ int uc_scene_render(uc_scene* l, const uint8_t* text, size_t text_stride, const 
   Path* prec = (Path*)sl->pinned;
   for (size_t k = 0; k < n_paths; ++k) {
     const uc_scene_path& q = paths[k];
-    prec[k].rate = (1.0 / fs_out) * (1.0 + (double)q.ppm * 1e-6);
-    prec[k].lead_s = q.lead_samples / fs_out;
+    const FrameOrigin fo = frame_origin(q.lead_samples, q.ppm, fs_out);
+    prec[k].rate = fo.rate;
+    prec[k].t0 = fo.t0;
+    prec[k].origin = fo.origin;
     prec[k].amp = (float)((double)q.gain * 1.4142135623730951);
     prec[k].n_on = 2u + c.n_preamble + 8u * text_len[q.tx];
     prec[k].tx = q.tx;

@@ -8,19 +8,20 @@
 // (microphone, tile) to a persistent grid.  No LDS, no barrier, no atomics.
 //
 // Path loop: the microphone index comes from blockIdx and the tile counter alone, so the microphone's record, its path
-// records (rate, lead_s, amp, n_on, tx: derived on the host) and the loop's trip count are the same in every lane: they
+// records (rate, t0, origin, amp, n_on, tx: derived on the host) and the loop's trip count are the same in every lane: they
 // are read through const __restrict__ pointers with wave-uniform indices, which the compiler turns into scalar loads
 // into scalar registers.  The vector side carries four accumulators next to the live set of the link kernel's signal_at.
 //
 // Silent paths: a short message sounds over a few dozen tiles of a long recording.  symbol_at(frame_time(j)) is
-// monotone in j, every rounding included (a product with a constant, a difference with a constant, a sum with a
-// constant, a product with a positive constant and floor are each monotone), so if the symbol index at the tile's first
+// monotone in j, every rounding included (an exact integer difference with a constant, its conversion to double, the sum
+// with the place in the quad, one fma with two constants, a sum with a constant, a product with a positive constant and floor are each monotone: the comment
+// at frame_time() gives the steps), so if the symbol index at the tile's first
 // and at its last sample lie on the same silent side of the frame, signal_at returns +0.0f at every sample between them.
 // The proof needs the skip check and signal_at to evaluate ONE function: both call frame_time() and symbol_at() of
-// uc_link_dev.hpp and nothing else, force-inlined into one kernel under one contraction setting, so both sites get the
-// same roundings (today: one double fma); an edit that computes a time any other way at one site breaks the proof, and
-// the chunking and model tests of tests/test_gpu_scene.py are what would show it.  The fmax / fmin form also covers a
-// negative rate.
+// uc_link_dev.hpp and nothing else, and frame_time() writes its one fma out, so both sites get the same rounding; an
+// edit that computes a time any other way at one site breaks the proof, and the chunking and model tests of
+// tests/test_gpu_scene.py and tests/test_gpu_far.py (a path long over, one not yet begun, far from sample 0) are what
+// would show it.  The fmax / fmin form also covers a negative rate.
 // Such a path is not evaluated; +0.0f is added in its place, so the bits are those of the definition.
 //
 // Sum: the accumulators start at -0.0f, the one float that x + acc leaves every x unchanged for (the signs of zeros
@@ -30,7 +31,8 @@
 // Noise: fma(sigma, z, sum), written out.  The link kernel writes `v += sigma * z` and leaves the form to the compiler's
 // contraction, which makes exactly this of it (its v is a select between 0 and amp * sin, so the product of the signal
 // cannot be the fused one); the one-path identity with uc_link_transmit rests on that and tests/test_gpu_scene.py holds
-// it.  The link kernel's source stays as it is because its machine code is pinned.
+// it.  (The link kernels' machine code was compared with an earlier build's once, when this file was written; no test holds
+// such a comparison, and the one-path identity is the check of the two forms.)
 #include <hip/hip_runtime.h>
 
 #include "uc_link_dev.hpp"
@@ -63,21 +65,21 @@ __global__ __launch_bounds__(THREADS) void scene_kernel(const Params p, const Mi
     if (j0 >= end) continue;
     const Mic mc = mics[m];
     // the tile's first and last sample (of the whole workgroup: uniform)
-    const double jt0 = (double)(tile_quad * 4u), jt1 = jt0 + (double)(4 * TILE_QUADS - 1);
-    const double jd = (double)j0;
+    const uint64_t jt0 = tile_quad * 4u, jt1 = jt0 + (uint64_t)(4 * TILE_QUADS - 4);   // its first and its last quad
     const float start = mc.n_paths ? -0.0f : 0.0f;
     float v[4] = {start, start, start, start};
     for (uint32_t k = 0; k < mc.n_paths; ++k) {
       const Path pt = paths[mc.first_path + k];
-      const double qa = symbol_at(p, frame_time(pt, jt0)), qb = symbol_at(p, frame_time(pt, jt1));
+      const double qa = symbol_at(p, frame_time(pt, quad_distance(pt, jt0), 0)), qb = symbol_at(p, frame_time(pt, quad_distance(pt, jt1), 3));
       if (fmax(qa, qb) < 1.0 || fmin(qa, qb) >= (double)pt.n_on) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) v[i] = add_rn(v[i], 0.0f);
         continue;
       }
       const uint8_t* __restrict__ tx = text + (size_t)pt.tx * p.text_stride;
+      const double d0 = quad_distance(pt, j0);
 #pragma unroll
-      for (int i = 0; i < 4; ++i) v[i] = add_rn(v[i], signal_at(p, pt, tx, pt.n_on, jd + (double)i));
+      for (int i = 0; i < 4; ++i) v[i] = add_rn(v[i], signal_at(p, pt, tx, pt.n_on, d0, i));
     }
     if (mc.sigma != 0.0f) {
       const Words w = philox4x32_10((uint32_t)quad, (uint32_t)(quad >> 32), m, 0u, (uint32_t)p.seed, (uint32_t)(p.seed >> 32));

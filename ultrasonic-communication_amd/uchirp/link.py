@@ -9,17 +9,19 @@ fractional lead, Philox4x32-10 and Box-Muller.  It is what the tests hold the ke
 a GPU can call; it is slow (one stream at a time) and never used by `Link`.
 """
 import ctypes as C
+from fractions import Fraction
 
 import numpy as np
 
 from . import tx
 from ._binding import Binding
 
-ABI_VERSION = 1
+ABI_VERSION = 2
 DTYPE_I32, DTYPE_F32, DTYPE_I16 = 0, 1, 3
 MAX_TEXT = 4096
+MAX_FIRST_SAMPLE, MAX_SAMPLES = 1 << 52, 1 << 40
 EXPORTS = ["uc_link_abi_version", "uc_link_last_error", "uc_link_default_config", "uc_link_create", "uc_link_destroy",
-           "uc_link_transmit", "uc_link_noise_words"]
+           "uc_link_transmit", "uc_link_noise_words", "uc_link_frame_origin"]
 
 
 class LinkConfig(C.Structure):
@@ -32,6 +34,11 @@ class LinkStream(C.Structure):
     """struct uc_link_stream (include/uchirp_link.h)."""
     _fields_ = [("lead_samples", C.c_double), ("amplitude", C.c_float), ("sigma", C.c_float), ("ppm", C.c_float),
                 ("text_len", C.c_uint32)]
+
+
+class LinkOrigin(C.Structure):
+    """struct uc_link_origin (include/uchirp_link.h)."""
+    _fields_ = [("origin", C.c_int64), ("t0", C.c_double), ("rate", C.c_double)]
 
 
 STREAM_DTYPE = np.dtype([("lead_samples", "<f8"), ("amplitude", "<f4"), ("sigma", "<f4"), ("ppm", "<f4"), ("text_len", "<u4")])
@@ -47,6 +54,7 @@ def _declare(L):
     L.uc_link_transmit.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_double,
                                    C.c_uint64, C.c_size_t, C.c_size_t, C.c_uint64, C.c_void_p]
     L.uc_link_noise_words.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_size_t, C.c_void_p, C.c_void_p]
+    L.uc_link_frame_origin.argtypes = [C.c_double, C.c_float, C.c_double, C.POINTER(LinkOrigin)]
 
 
 _so = Binding("link", LinkError, _declare)
@@ -59,6 +67,13 @@ def default_config(**over):
     for k, v in over.items():
         setattr(cfg, k, v)
     return cfg
+
+
+def frame_origin(lead_samples, ppm=0.0, fs_out=78125.0):
+    """uc_link_frame_origin: (origin, t0, rate) as the library derives them on the host; needs no GPU."""
+    o = LinkOrigin()
+    _check(lib().uc_link_frame_origin(float(lead_samples), float(ppm), float(fs_out), C.byref(o)), "uc_link_frame_origin")
+    return int(o.origin), float(o.t0), float(o.rate)
 
 
 def _as_bytes(t):
@@ -209,19 +224,42 @@ def normals(seed, stream_index, first_sample, n_samples):
     return z.reshape(-1)[lo:lo + n_samples], ur.reshape(-1)[lo:lo + n_samples]
 
 
+def origin_model(lead_samples, ppm=0.0, fs_out=78125.0):
+    """What uc_link_frame_origin states, from fractions: (origin, t0, rate).  origin is the library's own choice (the double
+    quotient lead / (1 + ppm / 1e6) to the nearest integer, ties to even, held to +-2^53); t0 is the rational
+    (origin (1 + ppm 10^-6) - lead) / fs_out rounded once; rate is the library's double expression."""
+    lead, ppm, fs_out = float(lead_samples), float(np.float32(ppm)), float(fs_out)
+    den = 1.0 + ppm / 1e6
+    q = lead / den if den != 0.0 else (0.0 if lead == 0.0 else float(np.copysign(np.inf, lead)))   # (Python raises where C gives inf)
+    origin = int(round(min(max(q, -2.0 ** 53), 2.0 ** 53)))
+    t0 = float((origin * (1 + Fraction(ppm) / 10 ** 6) - Fraction(lead)) / Fraction(fs_out))
+    return origin, t0, (1.0 / fs_out) * (1.0 + ppm * 1e-6)
+
+
 def signal(text, lead_samples=0.0, amplitude=tx.AMPLITUDE, ppm=0.0, n_samples=None, fs_out=78125.0, first_sample=0,
            fs_tx=tx.FS_TX, t_symbol=tx.T_SYMBOL, f0=tx.F0, f1=tx.F1, n_preamble=tx.N_PREAMBLE, n_guard=tx.N_GUARD):
-    """tx.render's law, operation for operation, with a clock offset and a fractional lead (float64 [n_samples])."""
+    """tx.render's law, operation for operation, with a clock offset and a fractional lead (float64 [n_samples]).  The
+    seconds since the frame began come from the integer distance of the sample to the frame's origin (origin_model), as
+    in the library, so their error is that of a time inside the frame wherever in a recording the frame lies."""
+    if n_samples is None:
+        n_seq = 2 + n_preamble + 8 * len(_as_bytes(text)) + n_guard
+        lead_s = float(lead_samples) / float(fs_out)
+        n_samples = int(np.floor((lead_s + n_seq * (int(t_symbol * fs_tx) / float(fs_tx))) * fs_out)) - int(first_sample)
+    origin, t0, rate = origin_model(lead_samples, ppm, fs_out)
+    d = np.arange(int(first_sample) - origin, int(first_sample) - origin + int(n_samples), dtype=np.int64)
+    tt = d.astype(np.float64) * rate + t0
+    return law(text, tt, amplitude, fs_tx, t_symbol, f0, f1, n_preamble, n_guard)
+
+
+def law(text, tt, amplitude=tx.AMPLITUDE, fs_tx=tx.FS_TX, t_symbol=tx.T_SYMBOL, f0=tx.F0, f1=tx.F1, n_preamble=tx.N_PREAMBLE,
+        n_guard=tx.N_GUARD):
+    """The frame at the times tt (float64 seconds since it began): what `signal` does with its times."""
     raw = _as_bytes(text)
     bits = np.unpackbits(np.frombuffer(raw, np.uint8)).astype(int) if raw else np.zeros(0, int)
     seq = np.concatenate([[-1], np.ones(n_preamble, int), [0], bits, -np.ones(n_guard, int)]).astype(int)
     n_sym = int(t_symbol * fs_tx)
     sym_dur = n_sym / float(fs_tx)
-    lead_s = float(lead_samples) / float(fs_out)
-    if n_samples is None:
-        n_samples = int(np.floor((lead_s + len(seq) * sym_dur) * fs_out)) - int(first_sample)
-    j = np.arange(int(first_sample), int(first_sample) + int(n_samples), dtype=np.float64)
-    tt = j / fs_out * (1.0 + float(ppm) * 1e-6) - lead_s
+    tt = np.asarray(tt, np.float64)
     idx = np.floor((tt + 1e-10) / sym_dur).astype(np.int64)
     valid = (idx >= 0) & (idx < len(seq))
     tau = np.maximum(tt - idx * sym_dur, 0.0)
