@@ -101,6 +101,8 @@ int uc_align_abi_version(void);
 const char* uc_align_last_error(void);
 /* -ENODEV ("no CPU path") when no GPU is visible */
 int uc_align_create(int device, uc_align** out);
+/* Waits for every call of the object still in flight, on whatever streams they were given (each call is ordered behind the
+ * call two before it, so the events of the last two cover all), then frees it.  NULL is allowed. */
 void uc_align_destroy(uc_align* align);
 
 /* The correlations of the definition for n_pairs pairs.  pairs is a HOST array: it is copied, with the records derived

@@ -80,6 +80,8 @@ int uc_array_abi_version(void);
 const char* uc_array_last_error(void);
 /* -ENODEV ("no CPU path") when no GPU is visible */
 int uc_array_create(int device, uc_array** out);
+/* Waits for every call of the object still in flight, on whatever streams they were given (each call is ordered behind the
+ * call two before it, so the events of the last two cover all), then frees it.  NULL is allowed. */
 void uc_array_destroy(uc_array* array);
 
 /* The coefficients of the definition; needs no GPU.  -EINVAL: a NULL pointer, delay_samples or weight not finite,

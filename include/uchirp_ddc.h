@@ -119,6 +119,8 @@ int uc_ddc_filter_row(const float* taps, int n_taps, int decim, const void* in, 
 
 /* An object on one device, without tap sets.  -EINVAL: out is NULL; -ENODEV ("no CPU path") when no GPU is visible. */
 int uc_ddc_create(int device, uc_ddc** out);
+/* Waits for the device, and with it for every call of the object on whatever stream it was given (a call that stages
+ * nothing leaves no event to wait for), then frees it.  NULL is allowed. */
 void uc_ddc_destroy(uc_ddc* ddc);
 
 /* Uploads n_sets tap sets of n_taps taps each (taps: n_sets x n_taps floats on the host) and the decimation; they replace the

@@ -133,6 +133,8 @@ int uc_duc_sum_row(const float* const* y, int n_chan, size_t n, void* out, int o
 
 /* An object on one device, without tap sets.  -EINVAL: out is NULL; -ENODEV ("no CPU path") when no GPU is visible. */
 int uc_duc_create(int device, uc_duc** out);
+/* Waits for the device, and with it for every call of the object on whatever stream it was given (a call that stages
+ * nothing leaves no event to wait for), then frees it.  NULL is allowed. */
 void uc_duc_destroy(uc_duc* duc);
 
 /* Uploads n_sets prototypes of k_taps * interp taps each (taps: n_sets x k_taps * interp floats on the host); they replace

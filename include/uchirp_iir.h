@@ -78,6 +78,8 @@ int uc_iir_filter_row(const float* sections, int n_sections, const void* in, int
 /* An object on one device, without coefficient sets.  -EINVAL: out is NULL; -ENODEV ("no CPU path") when no GPU is
  * visible. */
 int uc_iir_create(int device, uc_iir** out);
+/* Waits for the device, and with it for every call of the object on whatever stream it was given (a call that stages
+ * nothing leaves no event to wait for), then frees it.  NULL is allowed. */
 void uc_iir_destroy(uc_iir* iir);
 
 /* Uploads n_sets coefficient sets of n_sections sections each (sections: n_sets x n_sections x 5 floats on the host); they

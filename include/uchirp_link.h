@@ -95,6 +95,8 @@ int uc_link_default_config(uc_link_config* cfg);
 int uc_link_frame_origin(double lead_samples, float ppm, double fs_out, uc_link_origin* out);
 /* -ENODEV ("no CPU path") when no GPU is visible; -EINVAL for a config that is not a frame format */
 int uc_link_create(int device, const uc_link_config* cfg, uc_link** out);
+/* Waits for every call of the object still in flight, on whatever streams they were given (each call is ordered behind the
+ * call two before it, so the events of the last two cover all), then frees it.  NULL is allowed. */
 void uc_link_destroy(uc_link* link);
 
 /* Renders samples [first_sample, first_sample + n_samples) of every stream: stream s to out_dev + s * stride_elems

@@ -124,6 +124,8 @@ int uc_mf_abi_version(void);
 const char* uc_mf_last_error(void);
 /* -ENODEV ("no CPU path") when no GPU is visible */
 int uc_mf_create(int device, uc_mf** out);
+/* Waits for every call of the object still in flight, on whatever streams they were given (each call is ordered behind the
+ * call two before it, so the events of the last two cover all), then frees it.  NULL is allowed. */
 void uc_mf_destroy(uc_mf* mf);
 
 /* The hop and the segments of a call; needs no GPU.  *hop = S; the call's outputs are those of the segments
@@ -144,7 +146,8 @@ int uc_mf_select(const float* e, uint32_t hop, uint32_t lo, uint32_t hi, uc_mf_r
 int uc_mf_arrival(const uc_mf_candidate* cand, double* offset, double* height);
 
 /* The object's templates (see the definition).  taps is a HOST array.  Synchronous: it waits for the object's calls in
- * flight, and returns with the spectra on the device.  All or nothing: a refused call leaves the former templates in
+ * flight on whatever streams they were given (the events of the last two calls: each call is ordered behind the call two
+ * before it), and returns with the spectra on the device.  All or nothing: a refused call leaves the former templates in
  * place.  -EINVAL: a NULL pointer, n_sets not in 1 .. UC_MF_MAX_SETS, n_taps not in 1 .. UC_MF_MAX_TAPS, a tap that is
  * not finite. */
 int uc_mf_set_templates(uc_mf* mf, const float* taps, uint32_t n_sets, uint32_t n_taps);

@@ -85,6 +85,7 @@ int uc_mic_modulate_row(const int32_t* q, size_t n, int32_t state[4], uint32_t* 
 /* An object on one device.  -EINVAL: a scale that is not finite and positive, out is NULL; -ENODEV ("no CPU path") when no
  * GPU is visible. */
 int uc_mic_create(int device, float scale, uc_mic** out);
+/* Frees the object at once: it owns no device memory, so no call in flight reads anything of it.  NULL is allowed. */
 void uc_mic_destroy(uc_mic* mic);
 
 /* Modulates n_samples samples of n_rows rows.  in_dev (float or int32 by in_dtype), state_dev (n_rows x 4 int32, in and out:

@@ -106,6 +106,8 @@ int64_t uc_rate_count(const uc_rate_info* info, uint64_t n_in);
 /* An object for one ratio on one device; the table is computed and uploaded once.  -EINVAL as uc_rate_plan; -ENODEV ("no
  * CPU path") when no GPU is visible. */
 int uc_rate_create(int device, uint32_t up, uint32_t down, uint32_t half, double beta, uc_rate** out);
+/* Waits for the device, and with it for every call of the object on whatever stream it was given (a call that stages
+ * nothing leaves no event to wait for), then frees it.  NULL is allowed. */
 void uc_rate_destroy(uc_rate* rate);
 
 /* Writes samples [out_first, out_first + n_out) of n_rows rows.  in_dev and out_dev are device memory of the object's

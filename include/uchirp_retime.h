@@ -79,6 +79,8 @@ int uc_retime_abi_version(void);
 const char* uc_retime_last_error(void);
 /* -ENODEV ("no CPU path") when no GPU is visible */
 int uc_retime_create(int device, uc_retime** out);
+/* Waits for every call of the object still in flight, on whatever streams they were given (each call is ordered behind the
+ * call two before it, so the events of the last two cover all), then frees it.  NULL is allowed. */
 void uc_retime_destroy(uc_retime* retime);
 
 /* The two integers of the definition; needs no GPU.  -EINVAL: a NULL pointer, delay_samples or slope not finite,

@@ -91,6 +91,8 @@ int uc_scan_abi_version(void);
 const char* uc_scan_last_error(void);
 /* -ENODEV ("no CPU path") when no GPU is visible */
 int uc_scan_create(int device, uc_scan** out);
+/* Waits for the device, and with it for every call of the object on whatever stream it was given (a call that stages
+ * nothing leaves no event to wait for), then frees it.  NULL is allowed. */
 void uc_scan_destroy(uc_scan* scan);
 
 /* q = llrint(delay_samples * 256); needs no GPU.  -EINVAL: q NULL, delay_samples not finite or |delay_samples| > 2^20. */
@@ -107,7 +109,8 @@ int uc_scan_power_row(const void* in, int in_dtype, size_t n_rows, uint64_t in_f
                       size_t window_len, double* power);
 
 /* Replaces the object's steering set: mics, weights (n_taps each) and delays (n_beams rows of n_taps doubles,
- * delay_stride doubles apart; 0 means n_taps) are HOST arrays.  Synchronous, and all or nothing: a refused call
+ * delay_stride doubles apart; 0 means n_taps) are HOST arrays.  Synchronous (it waits for the device before
+ * it frees the old set, so no call in flight on any stream still reads it), and all or nothing: a refused call
  * (-EINVAL: a NULL pointer, n_taps not in 1 .. UC_SCAN_MAX_TAPS, n_beams not in 1 .. UC_SCAN_MAX_BEAMS, delay_stride <
  * n_taps, a weight or a delay that is not finite, |delay| > 2^20) leaves the old set in place. */
 int uc_scan_set_beams(uc_scan* scan, const uint32_t* mics, const float* weights, size_t n_taps, const double* delays,

@@ -75,6 +75,8 @@ const char* uc_scene_last_error(void);
 int uc_scene_default_config(uc_link_config* cfg);
 /* -ENODEV ("no CPU path") when no GPU is visible; -EINVAL for a config that is not a frame format */
 int uc_scene_create(int device, const uc_link_config* cfg, uc_scene** out);
+/* Waits for every call of the object still in flight, on whatever streams they were given (each call is ordered behind the
+ * call two before it, so the events of the last two cover all), then frees it.  NULL is allowed. */
 void uc_scene_destroy(uc_scene* scene);
 
 /* Renders samples [first_sample, first_sample + n_samples) of every microphone: microphone m to

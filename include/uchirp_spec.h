@@ -135,10 +135,13 @@ int uc_spec_plan(const uc_spec_params* params, size_t n_rows, size_t n_in, size_
 
 /* An object on one device; its window is the periodic Hann of 2048 values.  -ENODEV ("no CPU path") when no GPU is visible. */
 int uc_spec_create(int device, uc_spec** out);
+/* Waits for the device, and with it for every call of the object on whatever stream it was given (a call that stages
+ * nothing leaves no event to wait for), then frees it.  NULL is allowed. */
 void uc_spec_destroy(uc_spec* spec);
 
-/* The object's window: len floats of a host array, or -- window NULL -- the periodic Hann of len values.  Waits for the
- * object's calls in flight, then copies.  -EINVAL: spec NULL, len not in 1 .. 2048, a value that is not finite. */
+/* The object's window: len floats of a host array, or -- window NULL -- the periodic Hann of len values.  Synchronous: it
+ * waits for the device, and with it for every call of the object on whatever stream it was given, then copies.
+ * -EINVAL: spec NULL, len not in 1 .. 2048, a value that is not finite. */
 int uc_spec_set_window(uc_spec* spec, const float* window, size_t len);
 
 /* The spectra of the definition for n_frames frames of each of n_rows rows.  in_dev, out_dev and peaks_dev (or NULL) are

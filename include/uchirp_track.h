@@ -117,6 +117,8 @@ int uc_track_abi_version(void);
 const char* uc_track_last_error(void);
 /* -ENODEV ("no CPU path") when no GPU is visible */
 int uc_track_create(int device, uc_track** out);
+/* Waits for every call of the object still in flight, on whatever streams they were given (each call is ordered behind the
+ * call two before it, so the events of the last two cover all), then frees it.  NULL is allowed. */
 void uc_track_destroy(uc_track* track);
 
 /* The correlations and crest records of the definitions for n_pairs pairs and n_windows windows.  pairs is a HOST array: it

@@ -142,6 +142,8 @@ int uc_wcorr_abi_version(void);
 const char* uc_wcorr_last_error(void);
 /* -ENODEV ("no CPU path") when no GPU is visible */
 int uc_wcorr_create(int device, uc_wcorr** out);
+/* Waits for every call of the object still in flight, on whatever streams they were given (each call is ordered behind the
+ * call two before it, so the events of the last two cover all), then frees it.  NULL is allowed. */
 void uc_wcorr_destroy(uc_wcorr* wcorr);
 
 /* The correlations of the definition for n_pairs pairs and n_windows windows.  pairs and weights are HOST arrays: they are

@@ -99,6 +99,8 @@ int uc_xcorr_abi_version(void);
 const char* uc_xcorr_last_error(void);
 /* -ENODEV ("no CPU path") when no GPU is visible */
 int uc_xcorr_create(int device, uc_xcorr** out);
+/* Waits for every call of the object still in flight, on whatever streams they were given (each call is ordered behind the
+ * call two before it, so the events of the last two cover all), then frees it.  NULL is allowed. */
 void uc_xcorr_destroy(uc_xcorr* xcorr);
 
 /* The correlations of the definition for n_pairs pairs.  pairs is a HOST array: it is copied, with the records derived

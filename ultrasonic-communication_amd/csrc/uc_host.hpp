@@ -1,6 +1,6 @@
-// uc_host.hpp -- the host layer that the C-ABI files of the seven sibling libraries share (uc_link_api.cpp, uc_scene_api.cpp,
-// uc_array_api.cpp, uc_align_api.cpp, uc_xcorr_api.cpp, uc_retime_api.cpp, uc_track_api.cpp), so that their contracts cannot
-// drift apart:
+// uc_host.hpp -- the host layer that the C-ABI files of the sixteen sibling libraries share (uc_<name>_api.cpp for link,
+// scene, array, align, xcorr, wcorr, track, retime, rate, spec, mic, iir, scan, ddc, mf and duc), so that their contracts
+// cannot drift apart:
 //   errors     the thread's last error (fail, hip_fail) and the guard that restores the caller's HIP device
 //   the object HostBase, which every struct uc_<name> derives from; open() and close_base(), what every uc_*_create and
 //              uc_*_destroy does; DeviceBuffer, a device buffer per staging slot that grows; the transform's twiddles

@@ -205,6 +205,7 @@ void uc_rate_destroy(uc_rate* l) {
   if (!l) return;
   DeviceGuard guard;
   close_base(l);
+  (void)hipDeviceSynchronize();      // the calls stage nothing and leave no event to wait for
   if (l->table) (void)hipFree(l->table);
   delete l;
 }

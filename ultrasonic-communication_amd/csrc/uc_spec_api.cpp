@@ -2,9 +2,10 @@
 // parameter struct, the object with its window and twiddle table, the launch.  The object's base, create and destroy, the
 // grid and the checks of the row matrices are the shared host layer's (uc_host.hpp: header-only, nothing crosses a library
 // boundary): libuchirp_spec.so stands alone.  A call reads no host array but its parameter struct, which travels as kernel
-// arguments, so nothing is staged; of the base's first staging slot only the `done` event is used, as the mark behind the
-// object's last launch that uc_spec_set_window waits for.  No CPU compute path exists here: without a usable HIP device
-// uc_spec_create fails.  Every entry point leaves the calling thread's current HIP device as it found it.
+// arguments, so nothing is staged and the base's staging slots stay empty: a call leaves no event behind, and what must
+// wait for the object's calls (uc_spec_set_window, uc_spec_destroy) waits for the device, whatever streams they were given.
+// No CPU compute path exists here: without a usable HIP device uc_spec_create fails.  Every entry point leaves the calling
+// thread's current HIP device as it found it.
 #include "../../include/uchirp_spec.h"
 #include "uc_host.hpp"
 #include "uc_spec.hpp"
@@ -113,6 +114,7 @@ void uc_spec_destroy(uc_spec* l) {
   if (!l) return;
   DeviceGuard guard;
   close_base(l);
+  (void)hipDeviceSynchronize();      // the calls stage nothing and leave no event to wait for
   if (l->window) (void)hipFree(l->window);
   if (l->tw) (void)hipFree(l->tw);
   delete l;
@@ -129,8 +131,9 @@ int uc_spec_set_window(uc_spec* l, const float* window, size_t len) {
   DeviceGuard guard;
   hipError_t e = hipSetDevice(l->device);
   if (e != hipSuccess) return hip_fail(e, "uc_spec_set_window", "hipSetDevice");
-  StagingSlot& mark = l->slot[0];
-  if (mark.in_flight) (void)hipEventSynchronize(mark.done);              // the object's last launch has read the old window
+  // no launch may still read the old window, on whatever stream it was enqueued (an event behind the last launch would
+  // cover that launch's stream only: nothing orders one call behind the call before)
+  if ((e = hipDeviceSynchronize()) != hipSuccess) return hip_fail(e, "uc_spec_set_window", "hipDeviceSynchronize");
   // (pageable memory: done when the call returns)
   if ((e = hipMemcpy(l->window, w.data(), POINTS * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess)
     return hip_fail(e, "uc_spec_set_window", "hipMemcpy");
@@ -193,12 +196,8 @@ int uc_spec_run(uc_spec* l, const void* in_dev, int in_dtype, size_t n_rows, siz
   p.db_mul = params->db_mul;
   const uint64_t grid = persistent_grid(l, in_dtype, resident_blocks_per_cu, 4, n_units);
 
-  // ---- enqueue: the only launch, and behind it the mark that uc_spec_set_window and uc_spec_destroy wait for
-  hipStream_t hs = (hipStream_t)hip_stream;
-  e = (hipError_t)launch_spectra(in_dtype, (unsigned)grid, hs, p);
-  StagingSlot& mark = l->slot[0];
-  (void)hipEventRecord(mark.done, hs);
-  mark.in_flight = true;
+  // ---- enqueue: the only launch
+  e = (hipError_t)launch_spectra(in_dtype, (unsigned)grid, (hipStream_t)hip_stream, p);
   if (e != hipSuccess) return hip_fail(e, WHO, "launch");
   return 0;
 }
