@@ -33,7 +33,21 @@
  * 6 in the tree).  The segment sums are converted to double and added in double, starting from 0.0, in ascending
  * segment order.  So |r_p[l] - exact| <= K * 2^-24 * sum_j |x_ref[j] * x_mic[j + l]| to first order, and a result
  * depends on the inputs, the pair, first, n and L only: never on the grid, on which wave handled which segment, or on the
- * other pairs of the call.  Inputs are taken as finite.
+ * other pairs of the call.
+ *
+ * Non-finite samples.  One float sample x_m[q] that is NaN, +Inf or -Inf (integer words hold none):
+ *   MUST      r_p[l] is not finite wherever its sum has a term with x_m[q]: for every l if m is the pair's reference row and
+ *             first <= q < first + n (also where the other factor is a microphone sample outside the row, +0.0f); for the
+ *             lags with first <= q - l < first + n if m is the pair's microphone row.
+ *   MAY       if m is the pair's microphone row, also the lags with first + n <= q - l < first + n_up, where n_up is n with
+ *             its last segment rounded up to a multiple of 256 samples (n_up - n <= 255): a segment is walked in passes
+ *             of 256 reference samples, and in the last, partial pass the lanes behind the reference's end hold +0.0f and
+ *             still multiply the microphone samples opposite them (0 * NaN is NaN).  So the last microphone sample that
+ *             can reach a sum is first + n_up + L - 1, and it reaches lag +L alone.  Such a value is either bit for bit the
+ *             clean call's or not finite (this implementation: not finite), never another finite number.
+ *   MUST NOT  everything else the call writes -- the other lags of the pair, all other pairs, and every word of corr_dev
+ *             between the rows -- is bit for bit what the same call writes with a finite sample there.
+ * uc_align_peak refuses a correlation with a value that is not finite (-EINVAL): it is the host's detector.
  *
  * DEFINITION OF THE PEAK (uc_align_peak; double arithmetic on the host)
  *

@@ -38,6 +38,15 @@
  * for FINITE inputs: the chain still multiplies the 15 neighbouring samples by 0.0f, so an infinity or a NaN within
  * -7 .. +8 samples of a sample makes that output NaN (as it does for every fractional delay).
  *
+ * Non-finite samples.  One float sample x_m[q] that is NaN, +Inf or -Inf (integer words hold none):
+ *   MUST      output j of a beam is not finite wherever one of its taps k of microphone m has q under its sixteen
+ *             coefficients, j + shift_k <= q <= j + shift_k + 15 (shift_k from uc_array_tap_coefficients) -- also where
+ *             c_k[t] is zero, as fifteen are for an integer delay: 0 * NaN is NaN.
+ *   MAY       nothing: every chain is evaluated as it is written.
+ *   MUST NOT  every other output of the beam, the beams without a tap of microphone m, and every word of out_dev between
+ *             the rows: bit for bit what the same call writes with a finite sample there.  A sample whose supports all lie
+ *             outside [out_first, out_first + n_out) touches nothing.
+ *
  * OUT OF SCOPE: per-microphone clock offsets (an array shares one clock here; libuchirp_retime.so, uchirp_retime.h, puts
  * microphones with clocks of their own onto one first); estimating the delays (that is libuchirp_align.so, uchirp_align.h);
  * adaptive weights; output formats other than float; capture into a graph.

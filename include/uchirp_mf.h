@@ -15,7 +15,7 @@
  * Input.  n_rows rows in device memory: UC_MF_DTYPE_F32 (float), UC_MF_DTYPE_I32 (DFSDM words, each cast with (float)) or
  * UC_MF_DTYPE_C32 (interleaved float pairs I, Q: what UC_DDC_OUT_IQ writes).  Row r starts at in_dev + r * in_stride
  * (elements: words, or pairs) and holds n_in elements.  x_r[j] is element j as a complex number, with imaginary part +0
- * for the real types; outside [0, n_in) a row reads +0.  Inputs are taken as finite.
+ * for the real types; outside [0, n_in) a row reads +0.  What a float that is not finite does: "Non-finite samples" below.
  *
  * Templates.  uc_mf_set_templates(mf, taps, n_sets, n_taps): n_sets = 1 .. UC_MF_MAX_SETS sets of T = n_taps =
  * 1 .. UC_MF_MAX_TAPS complex taps h_s[t], a host array of n_sets * n_taps float pairs.  With P = UC_MF_POINTS = 2048,
@@ -58,6 +58,23 @@
  * never on the grid, on the other jobs or their order, or on the staging slot.  A segment that lies wholly in the range
  * of two calls, with its window inside the row in both, has the same bits in both: that is what a live caller who keeps
  * T samples of history gets.
+ *
+ * Non-finite samples.  One float of row r -- element q, or the real or the imaginary part of it alone -- that is NaN,
+ * +Inf or -Inf (integer words hold none), in every job { r, set }:
+ *   MUST      y of row element e is not finite in every format (the pair, its real part, its power, its magnitude) wherever its
+ *             sum has a term with x[q]: e - T + 1 <= q <= e, for the e inside the call's range.
+ *   MAY       all other outputs of a segment k whose WINDOW holds q, a_k = row elements k S - pos0 - T .. k S - pos0 + S,
+ *             cut at the row and not at the call's first + n: a segment comes out of one inverse transform (this
+ *             implementation: they are all not finite).  The window is one element wider on each side than the sums of
+ *             the segment's outputs reach (they read k S - pos0 - T + 1 .. k S - pos0 + S - 1; the two neighbours the
+ *             record looks at read the rest), and it reaches behind first + n: a sample no output of the call reads can
+ *             take a whole segment with it.  Such a value is either bit for bit the clean call's or not finite, never
+ *             another finite number.
+ *   MUST NOT  every segment whose window does not hold q, every other row's jobs, their records, and every word of out_dev
+ *             between the rows: bit for bit what the same call writes with a finite sample there.
+ * Record of a segment with a power that is not finite: n_cand = 0, four zero slots, count as usual, and a sum that is not
+ * finite (no comparison with a NaN holds, and +Inf is not greater than +Inf).  !isfinite(sum) is the caller's test: such a
+ * segment never reports a candidate.  A MAY segment's record is either that or bit for bit the clean one.
  *
  * Error.  With a_k the window and h the template,
  *   |y[q] - exact| <= UC_MF_ERROR_C * 2^-24 * ||a_k||_2 * ||h||_2.

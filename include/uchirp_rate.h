@@ -42,6 +42,15 @@
  * the other rows, or how the output range is cut into calls.  (The order ascends in the input index: a kernel that feeds a
  * banded coefficient tile to the f32 matrix instruction, itself an fmaf chain, meets it too, for finite inputs.)
  *
+ * Non-finite samples.  One float sample x[q] of row r that is NaN, +Inf or -Inf (int16 samples hold none):
+ *   MUST      output m of row r is not finite wherever its chain has a term with x[q]: k - T + 1 <= q <= k, with k the
+ *             newest input of m (uc_rate_step) -- all T taps, also where C[p][j] is zero (the taps behind the prototype's
+ *             end, the zeros of the sinc at integer phases): 0 * NaN is NaN.
+ *   MAY       nothing: the chain is evaluated as it is written, one accumulator per output and row.
+ *   MUST NOT  every other output of the row, every other row (the fifteen that share its block and its packed
+ *             multiply-adds among them), and every word of out_dev between the rows: bit for bit what the same call writes
+ *             with a finite sample there.
+ *
  * OUT OF SCOPE: ratios that change during a call (the retimer's job, uchirp_retime.h, behind this stage); output formats
  * other than float; a selection of rows; capture into a graph; filters other than the Kaiser family.
  */

@@ -42,6 +42,15 @@
  * for FINITE inputs (the chain still multiplies the 15 neighbouring samples by 0.0f).  slope = 0 and a delay of k + q / 256
  * give what uc_array_combine gives for one tap of weight 1 at that delay, bit for bit.
  *
+ * Non-finite samples.  One float sample x[i] of microphone m that is NaN, +Inf or -Inf (integer words hold none):
+ *   MUST      output j of a line of microphone m is not finite wherever I - 7 <= i <= I + 8, with I the integer of the
+ *             fixed-point step above -- all sixteen coefficients, also where c[t] is zero, as fifteen are on a whole
+ *             sample (q = 0 and mu = 0): 0 * NaN is NaN.
+ *   MAY       nothing: the chain is evaluated as it is written.
+ *   MUST NOT  every other output of the line, the lines of other microphones, and every word of out_dev between the
+ *             rows: bit for bit what the same call writes with a finite sample there.  A sample whose supports all lie
+ *             outside [out_first, out_first + n_out) touches nothing.
+ *
  * OUT OF SCOPE: ratios far from 1 (rate conversion between 44.1, 48 and 96 kHz needs other filters); estimating the line on
  * the GPU (uchirp/retime.py fits it on the host from the windows of libuchirp_align.so or libuchirp_xcorr.so); output formats
  * other than float; capture into a graph.

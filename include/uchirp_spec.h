@@ -46,6 +46,22 @@
  * STORED value and its bin; the lowest bin wins a tie (arm_max_f32, main.c:140).  A NaN is never the largest value; a frame
  * whose stored values are all NaN has { NaN, bin_first }.
  *
+ * Non-finite samples.  One float sample x_m[q] that is NaN, +Inf or -Inf (integer words hold none):
+ *   MUST      every frame f of row m with first + f * hop <= q < first + f * hop + frame_len has no finite X[k] -- also
+ *             where w[i] is zero, as the periodic Hann's w[0] is: 0 * NaN is NaN.  UC_SPEC_MAG and UC_SPEC_POWER store a
+ *             value that is not finite in every bin k >= ac_bins of such a frame (NaN for a NaN sample).  UC_SPEC_DB does
+ *             NOT: max(v, floor) sends a NaN magnitude to the floor, so such a bin stores db_mul * log10f(floor), the
+ *             level of silence, and +Inf where the magnitude is +Inf; a caller who must tell a dead microphone from a
+ *             silent one asks for UC_SPEC_MAG or UC_SPEC_POWER.  The bins k < ac_bins store their constant (1.0f, 1.0f,
+ *             db_mul * log10f(max(1.0f, floor))) in such a frame as in any other.
+ *   MAY       nothing: a frame has a transform of its own.
+ *   MUST NOT  every other frame of the row (a q that lies in a gap between frames touches none), every other row, their
+ *             peak records, and every word of out_dev between the frames: bit for bit what the same call writes with a
+ *             finite sample there.
+ * Peak of such a frame: the rule above over what is stored.  For a NaN sample that is { NaN, bin_first } under UC_SPEC_MAG
+ * and UC_SPEC_POWER if bin_first >= ac_bins, { 1.0f, bin_first } if the AC coupling covers bin_first; under UC_SPEC_DB the
+ * finite { larger of the AC constant and the floor level, bin_first }.
+ *
  * Invariance.  A frame's outputs depend on its samples, the window and the parameters only: never on the grid, the deal,
  * the other frames or rows of the call, or how a range of frames is cut into calls (first moved by whole hops).
  *

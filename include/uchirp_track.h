@@ -29,6 +29,19 @@
  * The arithmetic is that of uc_xcorr_correlate, so its error form carries over with UC_XCORR_ERROR_C = 11:
  *   |r[l] - exact| <= 11 * 2^-24 * E_p,   E_p = sum over the window's segments of ||a_s||_2 ||b_s||_2.
  *
+ * Non-finite samples.  One float sample x_m[q] that is NaN, +Inf or -Inf (integer words hold none); per (pair, window),
+ * with first' = first + w hop and n' = window_len, the zones of uchirp_xcorr.h:
+ *   MUST      r[l] is not finite wherever its sum has a term with x_m[q]: every l if m is the pair's reference row and
+ *             first' <= q < first' + n'; the lags with first' <= q - l < first' + n' if m is its microphone row.  The crest
+ *             record of such a (pair, window) has flags == UC_TRACK_NOT_FINITE alone and every other byte zero, and
+ *             uc_track_finish refuses it (-EINVAL): flags is the caller's test, on the device's record or on the host.
+ *   MAY       the other lags of such a (pair, window): its sums come out of one inverse transform per group (this
+ *             implementation: they are all not finite).  Each is bit for bit the clean call's or not finite.
+ *   MUST NOT  every (pair, window) that reads row m only outside the reference's [first', first' + n') and the
+ *             microphone's [first' - L, first' + n' + L) -- with overlapping windows a sample lies in several, with gaps
+ *             it may lie in none --, their crest records, and every word of corr_dev between the rows: bit for bit what
+ *             the same call writes with a finite sample there.
+ *
  * DEFINITION OF THE CREST RECORD (uc_track_crest; written by the device at crest_dev[p * n_windows + w])
  *
  * With r[k], k = 0 .. 2L, the doubles of one correlation:

@@ -65,7 +65,21 @@
  * cut into calls.  weights NULL and an explicit table of ones give the same bits; with guard 0 these are the bits of
  * uc_track_windows' correlations and of uc_xcorr_correlate, and with guard g the central 2 L + 1 values of
  * uc_xcorr_correlate at max_lag L + g.  Weights scaled by a power of two scale every result exactly (short of underflow
- * and overflow).  Weights of zero give 0.0.  Inputs are taken as finite.
+ * and overflow).  Weights of zero give 0.0 for finite inputs.
+ *
+ * Non-finite samples.  One float sample x_m[q] that is NaN, +Inf or -Inf (integer words hold none).  The definition
+ * above is total: a stored lag is a sum over every segment's whole 2048-point correlation, so every sample of a segment
+ * has a term in every stored lag of its (pair, window), whatever its coefficient h[u] -- with weights of ones h is the
+ * unit impulse and most of these coefficients are zero, with weights of zero all are: 0 * NaN is NaN, and the 0.0 of
+ * weights of zero becomes NaN.  With first' = first + w hop, n' = window_len and L' = max_lag + guard:
+ *   MUST      all 2 max_lag + 1 stored values of (pair, window) are not finite if m is the pair's reference row and
+ *             first' <= q < first' + n', or its microphone row and first' - L' <= q < first' + n' + L': the guard widens
+ *             the microphone's range, although its lags are not stored.
+ *   MAY       nothing.
+ *   MUST NOT  every other (pair, window) -- with overlapping windows a sample lies in several, with gaps it may lie in
+ *             none -- and every word of corr_dev between the rows: bit for bit what the same call writes with a finite
+ *             sample there.
+ * uc_wcorr_peak refuses a correlation with a value that is not finite (-EINVAL): it is the host's detector.
  *
  * Error.  With E_p = sum over s of ||a_s||_2 * ||b_s||_2 as in uchirp_xcorr.h at L',
  *   |r[l] - model| <= UC_WCORR_ERROR_C * 2^-24 * max_k |w[k]| * E_p.

@@ -34,7 +34,19 @@
  * float, bin by bin, in ascending segment order, and ONE inverse transform per group yields the 2 L + 1 float UNIT SUMS of
  * the group.  The unit sums are converted to double and added in double, starting from 0.0, in ascending group order.
  * A result depends on the inputs, the pair, first, n and L only: never on the grid, on which workgroup handled which
- * group, on the other pairs of the call or on their order.  Inputs are taken as finite.
+ * group, on the other pairs of the call or on their order.
+ *
+ * Non-finite samples.  One float sample x_m[q] that is NaN, +Inf or -Inf (integer words hold none):
+ *   MUST      r_p[l] is not finite wherever its sum has a term with x_m[q]: for every l if m is the pair's reference row and
+ *             first <= q < first + n (also where the other factor is a microphone sample outside the row, +0.0f); for the
+ *             lags with first <= q - l < first + n if m is the pair's microphone row.
+ *   MAY       the other lags of such a pair: the 2 L + 1 sums of a group come out of one inverse transform, so a pair that
+ *             has one MUST lag may be not finite at all its lags (this implementation: it is).  Such a value is either
+ *             bit for bit the clean call's or not finite, never another finite number.
+ *   MUST NOT  everything else the call writes -- the pairs that read row m only outside the reference's
+ *             [first, first + n) and the microphone's [first - L, first + n + L), all other pairs, and every word of
+ *             corr_dev between the rows -- is bit for bit what the same call writes with a finite sample there.
+ * uc_xcorr_peak refuses a correlation with a value that is not finite (-EINVAL): it is the host's detector.
  *
  * Error.  With E_p = sum over s of ||a_s||_2 * ||b_s||_2 (Euclidean norms; no product of a segment can exceed its term),
  *   |r_p[l] - exact| <= UC_XCORR_ERROR_C * 2^-24 * E_p.
