@@ -45,7 +45,7 @@
  *     chirps, tones, noise, DC and alternating inputs: |s1| <= 2.25 Y, |s2| <= 4.25 Y); int32 holds 64 Y.
  *
  * OUT OF SCOPE: microphone noise, DC offset and the acoustic overload point of a real part; other oversampling ratios than
- * 32; higher-order loops; PDM bit orders other than uc_dfsdm_sinc5's; capture into a graph.
+ * 32 (uc_dfsdm_run reads other ratios); higher-order loops; PDM bit orders other than uc_dfsdm_sinc5's; capture into a graph.
  */
 #ifndef UCHIRP_MIC_H
 #define UCHIRP_MIC_H
